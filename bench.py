@@ -21,6 +21,9 @@ traces of a synthetic rv64im loop executed by riscv_trace.py; `value` = cells/s)
 
 Usage: python bench.py --gpus N --steps K --warmup W     (N > 1: launched by torch.distributed.run, shards striped
 one per rank, no data-path collective). Prints ONE JSON line on rank 0; see DESIGN.md §8 for every field.
+A plain run sets up, warms up, times K proofs and prints the line (`verified` null, the extras' fields null); `--full` adds the
+pinned verifier on the last timed proof and the untimed extras (in-flight pool, program run, recursion machine, CPU baseline).
+`--dump-outputs DIR` writes the last timed step's proof and transcript state as DIR/*.npy.
 """
 import argparse
 import ctypes as C
@@ -250,6 +253,28 @@ def verify_proof(kind, proof, commit, state, L, lsh, names=(), vk_words=None):
         return False
     v = json.loads(r.stdout.strip().splitlines()[-1])
     return v["rc"] == 0 and v["state_matches"]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, proof, state, rank, world):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float arrays two builds can compare
+    exactly — the proof bytes (`proof`, float32, one element per byte) and the 34-word state the caller's challenger ends in
+    (`transcript_state`, float64). With --gpus N > 1 every rank writes its own shard's under a `_rank<r>` suffix. A proof too
+    large for the 64 MB budget is written as a fixed seeded sample of its bytes (`proof_sample`, positions in `proof_sample_index`)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    data = np.frombuffer(proof, np.uint8).astype(np.float32)
+    budget = DUMP_LIMIT_BYTES // world - 8 * len(state)
+    if data.nbytes <= budget:
+        np.save(os.path.join(out_dir, "proof%s.npy" % sfx), data)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(data.size, budget // 12, replace=False))
+        np.save(os.path.join(out_dir, "proof_sample%s.npy" % sfx), data[idx])
+        np.save(os.path.join(out_dir, "proof_sample_index%s.npy" % sfx), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "transcript_state%s.npy" % sfx), np.asarray(state, np.float64))
 
 
 def real_machine(api, repeat=4):
@@ -629,7 +654,17 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for the barrier / max-over-ranks (nccl = RCCL; gloo lets "
                          "several ranks share one GPU when testing the N > 1 path on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the pinned verifier on the last timed proof and the "
+                         "untimed extras (in-flight pool, commit-only, RS encode alone, host CPU, whole program run, recursion machine, "
+                         "CPU baseline; --no-verify / --no-extras / --no-cpu-baseline / --no-program-run still apply). A plain run sets "
+                         "up, warms up, times --steps proofs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64): "
+                         "the proof bytes and the transcript state the caller's challenger ends in")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.mode != "shard":
+        ap.error("--dump-outputs writes the last timed proof of --mode shard")
     if args.cpu_baseline_child is not None:
         return cpu_baseline_child(args.cpu_baseline_child)
     if args.verify_child is not None:
@@ -735,16 +770,18 @@ def main():
     tl = {name: timers_read(api, name) for name in TIMERS}
     dt = shards.max_over_ranks(dt)                 # shards are striped one per rank: no data-path collective
     timed_state = last_state[0].state()
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, proof, timed_state, rank, world)
 
-    # the pinned verifier on the LAST TIMED proof (rank 0, untimed): a line without `verified: true` is not printed
+    # --full: the pinned verifier on the LAST TIMED proof (rank 0, untimed): a line without `verified: true` is not printed
     verified = None
-    if rank == 0 and not args.no_verify:
+    if rank == 0 and args.full and not args.no_verify:
         verified = verify_proof(kind, proof, prep_commit, timed_state, L, lsh, names)
         if not verified:
             raise SystemExit("bench.py: the pinned verifier REJECTED the timed proof; no result line")
 
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:      # untimed extras; N > 1 runs measure scaling only
+    if rank == 0 and world == 1 and args.full and not args.no_extras:     # untimed extras; N > 1 runs measure scaling only
         extras["in_flight"] = in_flight(api, chips, area, L, lsh, max(4, args.steps), publics, meta.get("alu_events"))
         torch.cuda.synchronize()
         t1 = time.perf_counter()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Experiment (GPU box): where does per-proof time vary? Direct proofs on the default stream / on a side stream / through a
-1-slot pool, per-proof times, with the GPU's sclk + power sampled from OUR device's hwmon; then the same after forcing the
-performance level to high (if sysfs lets us). usage: python bench/exp_pool.py [scale_log2]"""
+1-slot pool, per-proof times, with the GPU's sclk + power sampled from OUR device's hwmon, at the device's own performance
+level (the script changes no device setting). usage: python bench/exp_pool.py [scale_log2]"""
 import os
 import sys
 import time
@@ -64,17 +64,3 @@ def run_all(tag):
 
 direct(2)
 run_all("auto:")
-s = B.GpuSampler()
-lvl = None
-if s.device:
-    lvl = "/sys/bus/pci/devices/%s/power_dpm_force_performance_level" % s.device
-try:
-    print("perf level was:", open(lvl).read().strip())
-    with open(lvl, "w") as f:
-        f.write("high")
-    print("perf level now:", open(lvl).read().strip())
-    run_all("high:")
-    with open(lvl, "w") as f:
-        f.write("auto")
-except Exception as e:
-    print("cannot force the performance level:", repr(e))

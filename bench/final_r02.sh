@@ -6,7 +6,7 @@ mkdir -p $out
 cd $GRAFT_REPO_ROOT
 timeout 1500 python -m pytest tests -m gpu -x -q > $out/final_pytest_gpu.txt 2>&1; tail -3 $out/final_pytest_gpu.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/final_smoke.txt 2>&1; tail -1 $out/final_smoke.txt
-timeout 600 python bench.py > $out/final_bench.json 2> $out/final_bench.err; cut -c1-300 $out/final_bench.json
+timeout 600 python bench.py --full > $out/final_bench.json 2> $out/final_bench.err; cut -c1-300 $out/final_bench.json
 timeout 300 python bench/bench_recursion.py --repeat 5 > $out/final_bench_recursion.txt 2>&1; tail -2 $out/final_bench_recursion.txt | cut -c1-400
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_stats

@@ -9,7 +9,7 @@
 out=$GRAFT_REPO_ROOT/gpurun_out/r03
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
-python bench.py > $out/bench.json 2> $out/bench.err
+python bench.py --full > $out/bench.json 2> $out/bench.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_stats
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o b -- python $GRAFT_REPO_ROOT/bench.py --steps 4 --warmup 1 --no-extras --no-verify > $out/bench_profiled_run.json 2>/dev/null

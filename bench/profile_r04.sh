@@ -11,7 +11,7 @@ cd $GRAFT_REPO_ROOT
 # the PMC table first: bench.py reads profiles/r04_traffic.json for the roofline object, and it must be the table of THIS build
 timeout 900 bash bench/pmc_traffic.sh $out/traffic.json > $out/traffic.log 2>&1
 cp $out/traffic.json profiles/r04_traffic.json
-timeout 600 python bench.py > $out/bench.json 2> $out/bench.err
+timeout 600 python bench.py --full > $out/bench.json 2> $out/bench.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_stats
 timeout 400 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d /tmp/prof_stats -o b -- python $GRAFT_REPO_ROOT/bench.py --steps 4 --warmup 1 --no-extras --no-verify > $out/bench_profiled_run.json 2>/dev/null

@@ -8,7 +8,7 @@ bash bench/pmc_traffic.sh $GRAFT_REPO_ROOT/$out/r05_traffic.json real > $out/pmc
 cp $out/r05_traffic.json profiles/r05_traffic.json
 bash bench/pmc_traffic.sh $GRAFT_REPO_ROOT/$out/r05_traffic_precompile.json precompile > $out/pmc_precompile.log 2>&1
 cp $out/r05_traffic_precompile.json profiles/r05_traffic_precompile.json
-timeout 900 python bench.py --steps 20 --warmup 5 > $out/r05_bench.json 2> $out/r05_bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $out/r05_bench.json 2> $out/r05_bench.err; echo "bench rc=$?"
 timeout 600 python bench.py --workload precompile --no-extras --steps 12 --warmup 3 > $out/r05_bench_precompile.json 2> $out/r05_bench_precompile.err; echo "precompile rc=$?"
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_real -o real -- python bench.py --no-extras --no-verify --steps 5 --warmup 1 > $out/prof_real.log 2>&1

@@ -7,7 +7,7 @@ out=gpurun_out/r06
 mkdir -p $out
 bash bench/pmc_traffic.sh $GRAFT_REPO_ROOT/$out/r06_traffic_fibonacci.json fibonacci > $out/pmc.log 2>&1
 cp $out/r06_traffic_fibonacci.json profiles/r06_traffic_fibonacci.json
-timeout 1500 python bench.py --steps 12 --warmup 3 > $out/r06_bench_fibonacci.json 2> $out/r06_bench_fibonacci.err; echo "bench rc=$?"
+timeout 1500 python bench.py --full --steps 12 --warmup 3 > $out/r06_bench_fibonacci.json 2> $out/r06_bench_fibonacci.err; echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o fib -- python bench.py --no-extras --no-verify --steps 5 --warmup 1 > $out/prof.log 2>&1
 find $out -name "*.db" -delete; find $out -name "*kernel_trace.csv" -delete

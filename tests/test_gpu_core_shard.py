@@ -78,7 +78,7 @@ def test_core_shaped_shard_at_a_64th_of_core_size_verifies(api):
 def test_core_shaped_shard_at_core_size_verifies(api):
     """The bench workload at the bench size: one core-shaped shard of 2^28 + 2^27 cells proven by
     sp1hip_prove_shard with the production parameters; the pinned verifier accepts, ends in the prover's transcript state,
-    and rejects the proof with one bit flipped. (bench.py runs the same check on its last timed proof.)"""
+    and rejects the proof with one bit flipped. (bench.py --full runs the same check on its last timed proof.)"""
     from core_shard import build_core_shard
     L, lsh = 22, 21
     chips, meta = build_core_shard(CORE_AREA, L)

@@ -54,7 +54,7 @@ def test_bench_line_through_rccl_at_one_gpu():
     (process-group init with device_id, barrier, max-over-ranks on a device tensor, destroy); the line carries
     `verified`, `host_threads` and `dist`."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--scale-log2", "4",
-                        "--no-extras", "--force-dist", "--backend", "nccl"], capture_output=True, text=True, timeout=600, env=_env())
+                        "--full", "--no-extras", "--force-dist", "--backend", "nccl"], capture_output=True, text=True, timeout=600, env=_env())
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = r.stdout.strip().splitlines()
     assert len(lines) == 1, "bench.py must print exactly one line on stdout:\n" + r.stdout[-2000:]

@@ -1,0 +1,173 @@
+#!/usr/bin/env python3
+"""The outer (BN254) commitment layer on one GPU: batched Poseidon2-BN254 permutations, outer Merkle commitments, outer
+commit_mles beside the inner (KoalaBear Poseidon2) commit_mles on the same input, and the device grind. Prints one JSON line.
+
+Every workload is timed (median of --repeat runs after one warm-up, host clock around a device synchronise), then — unless
+--no-pmc — run once more in a child process under `rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES` (a counter run of its own, no
+tracing) to get its VALU instructions per permutation (SQ_INSTS_VALU counts wave instructions; a wave carries 64
+permutations) and the fraction of the measured 32-bit integer add rate (profiles/r01_ubench_int.txt: 53.9 T lane-ops/s) that
+the timed run issued.
+
+  python bench/bench_outer.py [--repeat R] [--no-pmc] [--pmc-dir DIR]
+  python bench/bench_outer.py --one NAME        (one run of one workload: what the counter runs execute)
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ADD_RATE = 53.9438e12          # lane-ops/s, v_add_u32 (profiles/r01_ubench_int.txt)
+KB_P = 0x7F000001
+MERKLE = [(20, 16), (20, 64), (20, 256), (22, 64)]
+GRIND_BITS = 16
+
+
+def _workloads():
+    w = {"permute_2^22": None, "permute_2^22_lohi": None}
+    for lg, width in MERKLE:
+        w["merkle_2^%d_x%d" % (lg, width)] = (lg, width)
+    w["outer_commit_mles_2^20_b4_x64"] = None
+    w["inner_commit_mles_2^20_b4_x64"] = None
+    w["grind_%d" % GRIND_BITS] = None
+    return list(w)
+
+
+def _perms(name):
+    """Permutations one run performs (None: counted from the waves, see main)."""
+    if name.startswith("permute"):
+        return 1 << 22
+    if name.startswith("merkle") or name.startswith("outer_commit_mles"):
+        lg, width = (22, 64) if name.startswith("outer_commit") else next((l, w) for l, w in MERKLE if name == "merkle_2^%d_x%d" % (l, w))
+        h = 1 << lg
+        return h * ((width + 15) // 16) + (h - 1) + 2
+    return None
+
+
+class Runner:
+    def __init__(self):
+        import torch
+        from sp1_amd import api
+        self.torch, self.api = torch, api
+        torch.cuda.set_device(0)
+        self.g = torch.Generator(device="cuda").manual_seed(7)
+
+    def _kb(self, n):
+        t = self.torch
+        return t.randint(0, KB_P, (n,), generator=self.g, device="cuda", dtype=t.int64).to(t.int32)
+
+    def setup(self, name):
+        api, t = self.api, self.torch
+        if name.startswith("permute"):
+            n = 1 << 22
+            top = t.randint(0, 0x30644E72, (n, 3, 1), generator=self.g, device="cuda", dtype=t.int64).to(t.int32)
+            low = t.randint(-(1 << 31), (1 << 31) - 1, (n, 3, 7), generator=self.g, device="cuda", dtype=t.int64).to(t.int32)
+            states = t.cat([low, top], dim=2).reshape(-1).contiguous()           # each lane < p (top word below p's)
+            lohi = name.endswith("lohi")
+
+            def run():
+                os.environ["SP1HIP_OUTER_MUL"] = "lohi" if lohi else "mad"
+                api.outer_poseidon2_permute(states)
+            return run
+        if name.startswith("merkle"):
+            lg, width = next((l, w) for l, w in MERKLE if name == "merkle_2^%d_x%d" % (l, w))
+            cm = api.ColMajor(self._kb(width << lg), 1 << lg, width)
+            prover = api.OuterMerkleTcsProver()
+            return lambda: prover.commit_tensors([cm])
+        if name.endswith("commit_mles_2^20_b4_x64"):
+            mles = [api.ColMajor(self._kb(64 << 20), 1 << 20, 64)]
+            if name.startswith("outer"):
+                return lambda: api.outer_commit_mles(mles, 2)
+            prover = api.BasefoldProver(2, 124, 16)
+            return lambda: prover.commit_mles(mles)
+        if name.startswith("grind"):
+            def run():
+                ch = api.OuterChallenger()
+                ch.observe(list(range(1, 10)))
+                return ch.grind(GRIND_BITS)
+            return run
+        raise KeyError(name)
+
+    def time(self, name, repeat):
+        run = self.setup(name)
+        run()
+        self.torch.cuda.synchronize()
+        ts = []
+        for _ in range(repeat):
+            t0 = time.perf_counter()
+            run()
+            self.torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts.sort()
+        return ts[len(ts) // 2]
+
+
+def counters(name, pmc_dir):
+    """SQ_INSTS_VALU and SQ_WAVES summed over the outer_* kernels (the inner commit: every sp1hip kernel) of one run."""
+    d = os.path.join(pmc_dir, name.replace("^", ""))
+    shutil.rmtree(d, ignore_errors=True)
+    cmd = ["timeout", "-k", "10", "600", "rocprofv3", "--pmc", "SQ_INSTS_VALU", "SQ_WAVES", "--output-format", "csv", "-d", d,
+           "-o", "pmc", "--", sys.executable, os.path.abspath(__file__), "--one", name]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("counter run of %s failed (%d): %s" % (name, r.returncode, r.stderr[-2000:]))
+    want = (lambda k: "outer_" in k) if not name.startswith("inner") else (lambda k: "sp1hip" in k and "at::" not in k)
+    tot = {"SQ_INSTS_VALU": 0.0, "SQ_WAVES": 0.0}
+    for fn in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
+        for row in csv.DictReader(open(fn)):
+            if want(row["Kernel_Name"]) and row["Counter_Name"] in tot:
+                tot[row["Counter_Name"]] += float(row["Counter_Value"])
+    return tot
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--no-pmc", action="store_true")
+    ap.add_argument("--pmc-dir", default=None, help="where the counter runs write (default: a temporary directory, removed after)")
+    ap.add_argument("--one")
+    args = ap.parse_args()
+    if args.one:
+        r = Runner()
+        r.setup(args.one)()
+        r.torch.cuda.synchronize()
+        return
+    r = Runner()
+    out = {"workload": "outer (BN254) commitment layer", "gpus": 1}
+    times = {}
+    for name in _workloads():
+        times[name] = r.time(name, args.repeat if not name.startswith("merkle_2^22") else max(2, args.repeat // 2))
+        r.torch.cuda.empty_cache()
+    out["permute_2^22_per_s"] = round((1 << 22) / times["permute_2^22"] * 1e3)
+    out["permute_2^22_lohi_per_s"] = round((1 << 22) / times["permute_2^22_lohi"] * 1e3)
+    for name, ms in times.items():
+        if not name.startswith("permute"):
+            out[name + "_ms"] = round(ms, 3)
+    if not args.no_pmc:
+        valu = {}
+        pmc_dir = args.pmc_dir or tempfile.mkdtemp(prefix="outer_pmc_")
+        for name in _workloads():
+            c = counters(name, pmc_dir)
+            perms = _perms(name) or c["SQ_WAVES"] * 64                 # grind: one candidate per lane
+            if name.startswith("inner"):
+                valu[name] = {"valu_insts_per_row": round(c["SQ_INSTS_VALU"] * 64 / (1 << 22), 1)}
+                continue
+            per = c["SQ_INSTS_VALU"] * 64 / perms
+            valu[name] = {"valu_insts_per_perm": round(per), "perms": int(perms),
+                          "valu_fraction_of_add_rate": round(per * perms / (times[name] * 1e-3) / ADD_RATE, 3)}
+        out["pmc"] = valu
+        if args.pmc_dir is None:
+            shutil.rmtree(pmc_dir, ignore_errors=True)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -705,6 +705,48 @@ int sp1hip_pool_wait(sp1hip_pool_t* pool, sp1hip_ticket_t ticket, uint8_t* h_pro
 /* The same without blocking: SP1HIP_ERROR_NOT_READY while the shard is in flight. */
 int sp1hip_pool_try_wait(sp1hip_pool_t* pool, sp1hip_ticket_t ticket, uint8_t* h_proof, size_t* proof_len, sp1hip_pool_times_t* times);
 
+/* ---------------------------------------------------------------- outer (BN254) commitments and transcript
+ * The commitment scheme and transcript of the wrap proof (the reference's `SP1OuterGlobalContext`,
+ * /root/reference/slop/crates/bn254/src/lib.rs:L24-L90): Poseidon2 over the BN254 scalar field (width 3, x^5, 8 + 56 rounds),
+ * the sponge MultiField32PaddingFreeSponge<KB, Fr, Perm, 3, 16, 1> (16 KoalaBear elements per block, 8 packed into each of
+ * lanes 0 and 1 by reduce_31 = sum canonical(v_i) 2^(31 i)), compress = permute([l, r, 0])[0], and the transcript
+ * MultiField32Challenger<KB, Fr, Perm, 3, 2>. Every BN254 value that crosses this ABI is 8 little-endian u32 words in
+ * Montgomery form (R = 2^256, the Rust layout of Bn254Fr); KoalaBear words are Montgomery words (R = 2^32) as everywhere.
+ * PARITY: the permutation is pinned by its published test vector; the sponge, tree, commitment and challenger are pinned only by
+ * agreement of two reference statements (the device code and the in-circuit verifier), not by a reference output. */
+/* d_states [n][3][8] permuted in place (device); h_states the same on the host. */
+int sp1hip_outer_poseidon2_permute(uint32_t* d_states, size_t n, sp1hip_stream_t stream);
+int sp1hip_outer_poseidon2_permute_host(uint32_t* h_states, size_t n);
+/* d_tree: (2^(lg_height+1) - 1) x 8 words, one digest per node, leaf layer first (indexed like sp1hip_merkle_commit's tree).
+ * d_root_and_commit: 16 words, the root followed by compress(root, hash([lg_height, total_width])). */
+int sp1hip_outer_merkle_commit(const sp1hip_tensor_t* tensors, int n_tensors, int lg_height, uint32_t* d_tree,
+                               uint32_t* d_root_and_commit, sp1hip_stream_t stream);
+/* d_values: [n_idx][total_width] row-major (tensor order); d_paths: [n_idx][lg_height][8] sibling digests, leaf level first.
+ * Either output may be NULL. */
+int sp1hip_outer_merkle_open(const sp1hip_tensor_t* tensors, int n_tensors, int lg_height, const uint32_t* d_tree,
+                             const uint32_t* d_indices, size_t n_idx, uint32_t* d_values, uint32_t* d_paths,
+                             sp1hip_stream_t stream);
+/* KoalaBear RS encode (sp1hip_rs_encode_batch) of every mle into d_codewords[k] (2^(lg_n + lg_blowup) x width, column-major),
+ * then the outer tree over the codewords into d_tree; synchronises the stream to return the commitment (8 words). */
+int sp1hip_outer_commit_mles(const sp1hip_tensor_t* mles, int n_mles, int lg_n, int lg_blowup, uint32_t* const* d_codewords,
+                             uint32_t* d_tree, uint32_t h_commit[8], sp1hip_stream_t stream);
+/* The outer transcript (host). observe_commitment: the 8-word digest, observed as its four 64-bit chunks reduced into
+ * KoalaBear. grind: the SMALLEST witness w (canonical order) with check_witness(bits, w), searched on the device; returns it
+ * as a Montgomery word and leaves the challenger as check_witness would. state: out50 = sponge [3][8] Montgomery words,
+ * input length, input [16], output length, output [8] (the split form, popped from the end; unused entries zero). */
+typedef struct sp1hip_outer_challenger_s sp1hip_outer_challenger_t;
+int sp1hip_outer_challenger_new(sp1hip_outer_challenger_t** out);
+int sp1hip_outer_challenger_clone(const sp1hip_outer_challenger_t* ch, sp1hip_outer_challenger_t** out);
+void sp1hip_outer_challenger_free(sp1hip_outer_challenger_t* ch);
+int sp1hip_outer_challenger_observe(sp1hip_outer_challenger_t* ch, const uint32_t* felts, size_t n);
+int sp1hip_outer_challenger_observe_commitment(sp1hip_outer_challenger_t* ch, const uint32_t* digest8);
+int sp1hip_outer_challenger_sample(sp1hip_outer_challenger_t* ch, uint32_t* out);
+int sp1hip_outer_challenger_sample_ext(sp1hip_outer_challenger_t* ch, sp1hip_ext_t* out);
+int sp1hip_outer_challenger_sample_bits(sp1hip_outer_challenger_t* ch, int bits, uint32_t* out);
+int sp1hip_outer_challenger_check_witness(sp1hip_outer_challenger_t* ch, int bits, uint32_t witness, int* ok);
+int sp1hip_outer_challenger_grind(sp1hip_outer_challenger_t* ch, int bits, uint32_t* witness, sp1hip_stream_t stream);
+int sp1hip_outer_challenger_state(const sp1hip_outer_challenger_t* ch, uint32_t* out50);
+
 #ifdef __cplusplus
 }
 #endif

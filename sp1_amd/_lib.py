@@ -156,6 +156,22 @@ PROTOTYPES = [
     ("sp1hip_bb_merkle_commit", None, [C.POINTER(Tensor), _int, _int, _vp, _vp, _vp]),
     ("sp1hip_bb_commit_mles", None, [C.POINTER(Tensor), _int, _int, _int, C.POINTER(_vp), _vp, u32p, _vp]),
     ("sp1hip_bb_poseidon2_permute", None, [_vp, _sz, _vp]),
+    ("sp1hip_outer_poseidon2_permute", None, [_vp, _sz, _vp]),
+    ("sp1hip_outer_poseidon2_permute_host", None, [u32p, _sz]),
+    ("sp1hip_outer_merkle_commit", None, [C.POINTER(Tensor), _int, _int, _vp, _vp, _vp]),
+    ("sp1hip_outer_merkle_open", None, [C.POINTER(Tensor), _int, _int, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("sp1hip_outer_commit_mles", None, [C.POINTER(Tensor), _int, _int, _int, C.POINTER(_vp), _vp, u32p, _vp]),
+    ("sp1hip_outer_challenger_new", None, [C.POINTER(_vp)]),
+    ("sp1hip_outer_challenger_clone", None, [_vp, C.POINTER(_vp)]),
+    ("sp1hip_outer_challenger_free", "void", [_vp]),
+    ("sp1hip_outer_challenger_observe", None, [_vp, u32p, _sz]),
+    ("sp1hip_outer_challenger_observe_commitment", None, [_vp, u32p]),
+    ("sp1hip_outer_challenger_sample", None, [_vp, u32p]),
+    ("sp1hip_outer_challenger_sample_ext", None, [_vp, C.POINTER(Ext)]),
+    ("sp1hip_outer_challenger_sample_bits", None, [_vp, _int, u32p]),
+    ("sp1hip_outer_challenger_check_witness", None, [_vp, _int, C.c_uint32, C.POINTER(_int)]),
+    ("sp1hip_outer_challenger_grind", None, [_vp, _int, u32p, _vp]),
+    ("sp1hip_outer_challenger_state", None, [_vp, u32p]),
     ("sp1hip_poseidon2_permute_integer_form", None, [_vp, _sz, _vp]),
     ("sp1hip_poseidon2_permute_host", None, [_vp, _sz, _int]),
     ("sp1hip_host_permutation_is_vectorised", None, []),

@@ -812,3 +812,152 @@ def parse_zerocheck_proof(blob):
         chips.append(exts(u64()))
     assert o == len(blob)
     return point, chips
+
+
+# ---------------------------------------------------------------------------------------------------------- outer (BN254)
+# The commitment layer and transcript of the wrap proof (`SP1OuterGlobalContext`, /root/reference/slop/crates/bn254/src/lib.rs):
+# Poseidon2 over the BN254 scalar field, one BN254 element per Merkle digest, MultiField32Challenger. A BN254 value crosses the
+# ABI as 8 little-endian u32 words in Montgomery form (R = 2^256).
+OUTER_P = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+_OUTER_R = (1 << 256) % OUTER_P
+_OUTER_R_INV = pow(1 << 256, -1, OUTER_P)
+
+
+def outer_to_words(x):
+    """Python int (or a sequence of them) -> uint32 array [..., 8] of Montgomery words."""
+    if isinstance(x, (int, np.integer)):
+        m = int(x) % OUTER_P * _OUTER_R % OUTER_P
+        return np.array([(m >> (32 * i)) & 0xFFFFFFFF for i in range(8)], dtype=np.uint32)
+    return np.stack([outer_to_words(v) for v in x]) if len(x) else np.zeros((0, 8), np.uint32)
+
+
+def outer_from_words(w):
+    """uint32 array [..., 8] of Montgomery words -> Python int (or a nested list of them)."""
+    w = np.asarray(w, dtype=np.uint32)
+    if w.ndim == 1:
+        m = sum(int(w[i]) << (32 * i) for i in range(8))
+        return m * _OUTER_R_INV % OUTER_P
+    return [outer_from_words(v) for v in w]
+
+
+def outer_poseidon2_permute(states, stream=None):
+    """Device batch of permutations: states = device words [n * 24] (n states of 3 x 8 Montgomery words), in place."""
+    assert states.numel() % 24 == 0
+    check(_L().sp1hip_outer_poseidon2_permute(_dptr(states), states.numel() // 24, _stream_ptr(stream)))
+    return states
+
+
+class OuterMerkleTcsProver:
+    """Poseidon2Bn254 Merkle tensor commitment (the outer TCS prover): like MerkleTcsProver, one BN254 digest per node.
+    Roots, commitments and paths are 8-word Montgomery arrays."""
+
+    def commit_tensors(self, tensors, stream=None):
+        h = tensors[0].height
+        lg = h.bit_length() - 1
+        assert all(t.height == h for t in tensors) and 1 << lg == h
+        tree = device_words((2 * h - 1) * 8)
+        rc = device_words(16)
+        check(_L().sp1hip_outer_merkle_commit(_tensor_array(tensors), len(tensors), lg, _dptr(tree), _dptr(rc),
+                                              _stream_ptr(stream)))
+        rc_h = to_host(rc)
+        data = TcsProverData(tree, rc_h[:8].copy(), rc_h[8:].copy(), lg, sum(t.width for t in tensors))
+        return data.commit, data
+
+    def prove_openings_at_indices(self, data, indices, stream=None):
+        idx = to_device(np.asarray(indices, dtype=np.uint32))
+        paths = device_words(max(len(indices) * data.log_height * 8, 1))
+        none = (Tensor * 1)(Tensor(None, 0))
+        check(_L().sp1hip_outer_merkle_open(none, 1, data.log_height, _dptr(data.tree), _dptr(idx), len(indices), None,
+                                            _dptr(paths), _stream_ptr(stream)))
+        return dict(merkle_root=data.root, log_tensor_height=data.log_height, width=data.total_width,
+                    paths=to_host(paths)[:len(indices) * data.log_height * 8].reshape(len(indices), data.log_height, 8))
+
+    def compute_openings_at_indices(self, tensors, indices, stream=None):
+        idx = to_device(np.asarray(indices, dtype=np.uint32))
+        tw = sum(t.width for t in tensors)
+        lg = tensors[0].height.bit_length() - 1
+        vals = device_words(len(indices) * tw)
+        check(_L().sp1hip_outer_merkle_open(_tensor_array(tensors), len(tensors), lg, None, _dptr(idx), len(indices),
+                                            _dptr(vals), None, _stream_ptr(stream)))
+        return to_host(vals, (len(indices), tw))
+
+
+def outer_commit_mles(mles, log_blowup=2, stream=None):
+    """RS-encode every mle (the KoalaBear encoder of BasefoldProver.commit_mles) and commit the codewords with the outer tree.
+    Returns (commitment words, codewords as ColMajor, TcsProverData)."""
+    lg_n = mles[0].height.bit_length() - 1
+    assert all(m.height == 1 << lg_n for m in mles)
+    N = 1 << (lg_n + log_blowup)
+    cws = [ColMajor(device_words(N * m.width), N, m.width) for m in mles]
+    ptrs = (C.c_void_p * len(cws))(*[c.words.data_ptr() for c in cws])
+    tree = device_words((2 * N - 1) * 8)
+    commit = np.zeros(8, np.uint32)
+    check(_L().sp1hip_outer_commit_mles(_tensor_array(mles), len(mles), lg_n, log_blowup, ptrs, _dptr(tree),
+                                        commit.ctypes.data_as(_lib.u32p), _stream_ptr(stream)))
+    return commit, cws, TcsProverData(tree, None, commit, lg_n + log_blowup, sum(m.width for m in mles))
+
+
+class OuterChallenger:
+    """MultiField32Challenger<KoalaBear, Bn254Fr, Poseidon2Bn254, 3, 2> (host transcript, device grind). Observes and samples
+    KoalaBear Montgomery words like DuplexChallenger; observe_commitment takes an 8-word BN254 digest."""
+
+    def __init__(self, handle=None):
+        if handle is None:
+            handle = C.c_void_p()
+            check(_L().sp1hip_outer_challenger_new(C.byref(handle)))
+        self.h = handle
+
+    def clone(self):
+        out = C.c_void_p()
+        check(_L().sp1hip_outer_challenger_clone(self.h, C.byref(out)))
+        return OuterChallenger(out)
+
+    def observe(self, felts):
+        a = np.ascontiguousarray(np.asarray(felts, dtype=np.uint32).reshape(-1))
+        check(_L().sp1hip_outer_challenger_observe(self.h, a.ctypes.data_as(_lib.u32p), a.size))
+
+    def observe_commitment(self, digest):
+        a = np.ascontiguousarray(np.asarray(digest, dtype=np.uint32).reshape(8))
+        check(_L().sp1hip_outer_challenger_observe_commitment(self.h, a.ctypes.data_as(_lib.u32p)))
+
+    def sample(self):
+        out = C.c_uint32()
+        check(_L().sp1hip_outer_challenger_sample(self.h, C.byref(out)))
+        return out.value
+
+    def sample_ext_element(self):
+        e = Ext()
+        check(_L().sp1hip_outer_challenger_sample_ext(self.h, C.byref(e)))
+        return np.array(list(e.c), dtype=np.uint32)
+
+    def sample_point(self, n):
+        return np.stack([self.sample_ext_element() for _ in range(n)]) if n else np.zeros((0, 4), np.uint32)
+
+    def sample_bits(self, bits):
+        out = C.c_uint32()
+        check(_L().sp1hip_outer_challenger_sample_bits(self.h, bits, C.byref(out)))
+        return out.value
+
+    def check_witness(self, bits, witness):
+        ok = C.c_int()
+        check(_L().sp1hip_outer_challenger_check_witness(self.h, bits, C.c_uint32(int(witness)), C.byref(ok)))
+        return bool(ok.value)
+
+    def grind(self, bits, stream=None):
+        """The smallest witness (a Montgomery word), found on the device; the challenger ends as after check_witness."""
+        out = C.c_uint32()
+        check(_L().sp1hip_outer_challenger_grind(self.h, bits, C.byref(out), _stream_ptr(stream)))
+        return out.value
+
+    def state(self):
+        out = np.zeros(50, np.uint32)
+        check(_L().sp1hip_outer_challenger_state(self.h, out.ctypes.data_as(_lib.u32p)))
+        return out
+
+    def __del__(self):
+        if getattr(self, "h", None) and _L is not None:
+            try:
+                _L().sp1hip_outer_challenger_free(self.h)
+            except TypeError:                    # interpreter shutdown: the module globals are already gone
+                pass
+            self.h = None

@@ -80,6 +80,26 @@ def test_host_permutation_matches_model_on_random_states(lib):
     assert _host_permute(lib, states) == [M.permute(s) for s in states]
 
 
+def _gnark_kat():
+    """The second published vector (tests/golden/outer_poseidon2_kat.json: SP1's gnark test of the permutation)."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "outer_poseidon2_kat.json")) as f:
+        v = json.load(f)["vectors"]
+    return [([int(x, 16) for x in t["input"]], [int(x, 16) for x in t["output"]]) for t in v]
+
+
+def test_model_reproduces_the_gnark_known_answer():
+    kats = _gnark_kat()
+    assert [i for i, _ in kats] == [[0, 0, 0]]
+    for i, o in kats:
+        assert M.permute(i) == o
+
+
+def test_host_permutation_gnark_known_answer(lib):
+    kats = _gnark_kat()
+    assert _host_permute(lib, [i for i, _ in kats]) == [o for _, o in kats]
+
+
 class _Lib:
     """The host challenger through the raw C ABI (no torch, no device)."""
 

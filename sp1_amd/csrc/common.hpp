@@ -5,6 +5,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 
 #include "../../include/sp1hip.h"
@@ -20,6 +21,17 @@ template <class T> __device__ __forceinline__ const __attribute__((address_space
 }
 template <class T> __device__ __forceinline__ __attribute__((address_space(1))) T* gptr(T* p) {
     return (__attribute__((address_space(1))) T*)p;
+}
+
+// SP1HIP_* run-time switches. env_flag: "0..." = off, "1..." = on, unset or anything else = dflt; env_uint: a decimal number. A
+// switch that the tests flip inside one process is read on every call, every other one once (`static const` where it is read).
+inline bool env_flag(const char* name, bool dflt) {
+    const char* e = getenv(name);
+    return e && (e[0] == '0' || e[0] == '1') ? e[0] == '1' : dflt;
+}
+inline uint64_t env_uint(const char* name, uint64_t dflt) {
+    const char* e = getenv(name);
+    return e ? strtoull(e, nullptr, 10) : dflt;
 }
 
 void set_error(const char* fmt, ...);

@@ -586,14 +586,8 @@ template <int FV, int SV, bool FIRST, bool NBASE, bool FLAT>
 __global__ __launch_bounds__(256) void gkr_pass(const PassDesc* __restrict__ descs, const Ext* __restrict__ eq_int,
                                                 const Ext* __restrict__ T, const Ext* __restrict__ TL, Ext a0, Ext a1,
                                                 uint32_t* __restrict__ partials, RoundSync rs, uint32_t seq, uint32_t K,
-                                                uint32_t tile_size, FlatArgs fa, GateArg gate) {
+                                                uint32_t tile_size, FlatArgs fa) {
     static_assert(FV + SV > 0 && FV <= 2 && SV <= 2, "a pass folds and / or sums");
-    if (FV > 0 && gate.block != nullptr) {                   // enqueued one hand-over early: the challenges arrive through the gate
-        __shared__ uint32_t gate_words[8];
-        gate_wait_load(gate, gate_words, 8);
-        a0 = Ext{{gate_words[0], gate_words[1], gate_words[2], gate_words[3]}};
-        a1 = Ext{{gate_words[4], gate_words[5], gate_words[6], gate_words[7]}};
-    }
     constexpr int SVS = SV == 0 ? 1 : SV;                    // (types only; SV = 0 never touches the grid)
     GridAcc<SVS> g;
     grid_init<SVS>(g);
@@ -813,7 +807,7 @@ int sp1hip_logup_gkr_prove(const sp1hip_gkr_chip_t* chips, int n_chips, int max_
     SP1HIP_REQUIRE(L >= 1 && L <= 30, "max_log_row_count out of range");
     hipStream_t s = S(stream);
     // SP1HIP_GKR_DEBUG=1: host-side phase times on stderr (where a stage's non-kernel time goes)
-    static const bool gkr_debug = getenv("SP1HIP_GKR_DEBUG") != nullptr;
+    static const bool gkr_debug = env_flag("SP1HIP_GKR_DEBUG", false);
     auto t_last = std::chrono::steady_clock::now();
     auto mark = [&](const char* what) {
         if (!gkr_debug) return;
@@ -928,7 +922,7 @@ int sp1hip_logup_gkr_prove(const sp1hip_gkr_chip_t* chips, int n_chips, int max_
     // fraction tree run: on `s` the copy sat between the last tree kernel and the first hand-over (0.2 ms of an idle GPU).
     // Their buffer is taken from the arena HERE, before anything of this call is enqueued, and the side stream waits for
     // this point of `s` — a recycled block's previous user is then out of the way (the arena orders reuse by stream).
-    const uint32_t FLAT_MAX_SLOTS = [] { const char* e = getenv("SP1HIP_GKR_FLAT_SLOTS"); return e ? (uint32_t)atoi(e) : 65536u; }();   // read per call (tests)
+    const uint32_t FLAT_MAX_SLOTS = (uint32_t)env_uint("SP1HIP_GKR_FLAT_SLOTS", 65536);   // read per call (tests)
     size_t n_passes_total = 0;
     for (int v = 1; v <= L - 1; v++) n_passes_total += (size_t)(v + 1) / 2 + 1;     // (0, .), the folds in pairs, the last fold
     hipStream_t side = nullptr;
@@ -979,7 +973,7 @@ int sp1hip_logup_gkr_prove(const sp1hip_gkr_chip_t* chips, int n_chips, int max_
         // L >= 3: the first layer and the two levels below it come out of ONE pass over the traces (first_layers_kernel), the
         // rest of the tree two levels per launch (transition2_kernel; a last single level by transition_kernel). SP1HIP_GKR_FUSED=0:
         // the separate kernels (first_layer_kernel, one transition launch per level) — same words in every level (tests)
-        fused_tree = L >= 3 && [] { const char* e = getenv("SP1HIP_GKR_FUSED"); return !e || atoi(e) != 0; }();
+        fused_tree = L >= 3 && env_flag("SP1HIP_GKR_FUSED", true);
         if (fused_tree) {
             std::vector<FirstDesc> fdescs(K);
             for (uint32_t i = 0; i < K; i++)
@@ -1078,7 +1072,7 @@ int sp1hip_logup_gkr_prove(const sp1hip_gkr_chip_t* chips, int n_chips, int max_
     // tail better (sweep of round 2 on the one-round kernels: 4096 best, flat between 2048 and 8192). Round 4, two-round passes on
     // the real-chip shard (alternating runs on three boxes): 1024-3072 tiles are within 0.3 ms of each other, 4096 is 0.7-1.0 ms
     // slower over the stage, 8192 / 16384 1.4 / 3.2 ms slower — a pass carries more state per workgroup than a round kernel did.
-    static const uint32_t TARGET_TILES = [] { const char* e = getenv("SP1HIP_GKR_TILES"); return e ? std::max<uint32_t>((uint32_t)atoi(e), 1u) : 2048u; }();
+    constexpr uint32_t TARGET_TILES = 2048;
     std::vector<PassDesc> all_descs;
     all_descs.reserve(n_passes_total * K);                  // ~10 MB at 730 interactions: no regrowth copies while planning
     // a layer's last fold (one row per interaction) goes straight to the mailbox slot, 16-byte aligned behind word 0
@@ -1166,15 +1160,6 @@ int sp1hip_logup_gkr_prove(const sp1hip_gkr_chip_t* chips, int n_chips, int max_
     size_t launch_idx = 0;                                   // next pass: shapes[launch_idx], K descriptors of d_all
     RoundSyncHost rsync;
     SP1HIP_TRY(rsync.init(s));
-    // SP1HIP_GATE=1 (off by default): small passes are enqueued one hand-over early and wait for their challenges at a HostGate
-    // (round_sync.hpp), so that the dispatch of a pass overlaps the host's half of the round trip. Measured on the fibonacci shard
-    // (eight alternating runs): 25.3-25.6 ms with the gate against 24.5-25.1 without — the two reads of mapped host memory a gated
-    // workgroup starts with (ticket, then challenges: ~2 us each across PCIe) cost what the overlapped dispatch saves. Kept as an
-    // A/B knob; the proof bytes are the same either way (tests/test_gpu_gkr.py). SP1HIP_GATE_MAX_TILES: what "small" means.
-    const bool gate_on = [] { const char* e = getenv("SP1HIP_GATE"); return e && e[0] == '1'; }();
-    const uint32_t gate_max_tiles = [] { const char* e = getenv("SP1HIP_GATE_MAX_TILES"); return e ? (uint32_t)strtoul(e, nullptr, 10) : 256u; }();
-    HostGate gate;                                           // (declared after rsync / mb: destroyed first, so an early exit opens it before they drain)
-    if (gate_on) SP1HIP_TRY(gate.init(s));
     const Ext one = kb::ext_one(), zero = kb::ext_zero(), inv8 = kb::ext_inv(ext_c(8)), inv2 = kb::ext_inv(ext_c(2)), four = ext_c(4);
     uint32_t h_sums[40];
     // the cubic  scale (1 - pt + (2 pt - 1) X) (q0 + q1 X + q2 X^2)
@@ -1246,9 +1231,8 @@ int sp1hip_logup_gkr_prove(const sp1hip_gkr_chip_t* chips, int n_chips, int max_
         Ext a0 = zero, a1 = zero;                            // the challenges the next pass folds with
         int t = v;                                           // row variables not yet bound by a FOLD
         size_t final_rows_total = 0;
-        // one pass of the layer: shapes[idx], t_after = row variables left once it has folded. gate_slot: the pass is enqueued behind
-        // a HostGate and reads its challenges there; else they are the arguments. *seq_out = the number of its hand-over (sv > 0).
-        auto launch_pass = [&](size_t idx, int t_after, GateArg gate_arg, const Ext& c0, const Ext& c1, uint32_t* seq_out) -> int {
+        // one pass of the layer: shapes[idx], t_after = row variables left once it has folded; c0, c1 = the challenges it folds with
+        auto launch_pass = [&](size_t idx, int t_after, const Ext& c0, const Ext& c1) -> int {
             const PassShape shape = shapes[idx];
             const PassDesc* d_descs = (const PassDesc*)d_all.p + idx * K;
             const int fv = shape.fv, sv = shape.sv;
@@ -1257,11 +1241,10 @@ int sp1hip_logup_gkr_prove(const sp1hip_gkr_chip_t* chips, int n_chips, int max_
             const bool publish_rows = sv == 0 && direct_final;
             if (publish_rows) { rsync.pending = true; mb.pending = true; }       // (an early error return must drain the stream first)
             const RoundSync rs = sv > 0 ? rsync.next() : publish_rows ? RoundSync{rsync.d_counter, (volatile uint32_t*)mb.h_slot} : RoundSync{};
-            *seq_out = rsync.seq;
             const Ext* Tp = sv > 0 ? T_of(t_after - sv) : (const Ext*)nullptr;
             const Ext* TLp = sv > 0 ? TL_of(t_after - sv) : (const Ext*)nullptr;
             ScopedTimer tm(fv == 0 ? "gkr_pass_sum" : sv == 0 ? "gkr_pass_fold" : "gkr_pass_fold_sum", s);
-#define SP1HIP_GKR_PASS(FV, SV, F, NB, FL) hipLaunchKernelGGL((gkr_pass<FV, SV, F, NB, FL>), dim3(shape.tiles), dim3(256), 0, s, d_descs, (const Ext*)d_eq_int.p, Tp, TLp, c0, c1, d_partials.u32(), rs, publish_rows ? mb.seq + 1 : rsync.seq, K, shape.tile_size, fa, gate_arg)
+#define SP1HIP_GKR_PASS(FV, SV, F, NB, FL) hipLaunchKernelGGL((gkr_pass<FV, SV, F, NB, FL>), dim3(shape.tiles), dim3(256), 0, s, d_descs, (const Ext*)d_eq_int.p, Tp, TLp, c0, c1, d_partials.u32(), rs, publish_rows ? mb.seq + 1 : rsync.seq, K, shape.tile_size, fa)
 #define SP1HIP_GKR_PASS_FL(FV, SV, F, NB) do { if (shape.flat) SP1HIP_GKR_PASS(FV, SV, F, NB, true); else SP1HIP_GKR_PASS(FV, SV, F, NB, false); } while (0)
 #define SP1HIP_GKR_PASS_SRC(FV, SV) do { if (nbase) SP1HIP_GKR_PASS_FL(FV, SV, true, true); else if (shape.first) SP1HIP_GKR_PASS_FL(FV, SV, true, false); else SP1HIP_GKR_PASS_FL(FV, SV, false, false); } while (0)
             if (fv == 0 && sv == 2) { if (nbase) SP1HIP_GKR_PASS_FL(0, 2, true, true); else SP1HIP_GKR_PASS_FL(0, 2, true, false); }
@@ -1277,8 +1260,6 @@ int sp1hip_logup_gkr_prove(const sp1hip_gkr_chip_t* chips, int n_chips, int max_
             SP1HIP_LAUNCH_CHECK();
             return SP1HIP_SUCCESS;
         };
-        bool pre = false;                                    // the pass about to be handled is already enqueued (behind the gate, opened)
-        uint32_t pre_ticket = 0, pre_seq = 0;
         for (;;) {                                           // the passes of the layer (two rounds each)
             const PassShape shape = shapes[launch_idx];
             const size_t idx = launch_idx++;
@@ -1288,22 +1269,13 @@ int sp1hip_logup_gkr_prove(const sp1hip_gkr_chip_t* chips, int n_chips, int max_
             const auto dbg_l0 = std::chrono::steady_clock::now();
             if (gkr_debug && dbg_pass_pending) dbg_host += std::chrono::duration<double, std::milli>(dbg_l0 - dbg_pass_t).count();
             dbg_pass_pending = false;
-            uint32_t my_seq = pre_seq;
-            if (!pre) SP1HIP_TRY(launch_pass(idx, t, GateArg{nullptr, 0u}, a0, a1, &my_seq));
-            pre = false;
+            SP1HIP_TRY(launch_pass(idx, t, a0, a1));
             if (gkr_debug) dbg_launch += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - dbg_l0).count();
             build_eq_tabs();                                 // (first pass of the layer only) host work behind a running kernel
             if (sv == 0) break;
-            // the NEXT pass, one hand-over early when it is small (its duration is latency: the launch would be on the critical path)
-            if (gate_on && shapes[launch_idx].tiles <= gate_max_tiles) {
-                const GateArg ga = gate.arm();
-                pre_ticket = ga.ticket;
-                pre = true;                                  // (armed: from here on the ticket must be opened, whatever happens)
-                SP1HIP_TRY(launch_pass(launch_idx, t - shapes[launch_idx].fv, ga, zero, zero, &pre_seq));
-            }
             const int ns = sv == 2 ? 10 : 4;
             const auto dbg_w0 = std::chrono::steady_clock::now();
-            SP1HIP_TRY(rsync.wait_for(my_seq, h_sums, 4 * ns));
+            SP1HIP_TRY(rsync.wait(h_sums, 4 * ns));
             if (gkr_debug) { const auto now = std::chrono::steady_clock::now(); dbg_wait += std::chrono::duration<double, std::milli>(now - dbg_w0).count(); dbg_pass_t = now; dbg_passes++; dbg_pass_pending = true; }
             Ext S[10];
             memcpy(S, h_sums, 16 * (size_t)ns);
@@ -1349,11 +1321,6 @@ int sp1hip_logup_gkr_prove(const sp1hip_gkr_chip_t* chips, int n_chips, int max_
                 alphas.push_back(a0);
                 claim = poly_eval(poly, a0);
                 PA = PA * (pt_a * a0 + (one - pt_a) * (one - a0));
-            }
-            if (pre) {                                       // the armed pass starts now
-                uint32_t words[8];
-                memcpy(words, a0.c, 16); memcpy(words + 4, a1.c, 16);
-                gate.open(pre_ticket, words, 8);
             }
         }
         // the layer's last fold left one row per interaction: dense over 2^niv on the host

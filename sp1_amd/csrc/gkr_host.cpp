@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "common.hpp"
 #include "kb31.hpp"
 
 namespace sp1hip {
@@ -143,8 +144,7 @@ GKRH_TARGET void fold_avx512(const uint32_t* tab, uint32_t* out, size_t stride, 
 bool simd_ok() {
     static const bool cpu = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512dq") && __builtin_cpu_supports("avx512vl") &&
                             __builtin_cpu_supports("avx512bw");
-    const char* e = getenv("SP1HIP_HOST_SIMD");           // read per call: the GPU tests prove with both paths in one process
-    return cpu && !(e && atoi(e) == 0);
+    return cpu && sp1hip::env_flag("SP1HIP_HOST_SIMD", true);   // read per call: the GPU tests prove with both paths in one process
 }
 
 }  // namespace

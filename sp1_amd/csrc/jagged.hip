@@ -223,6 +223,7 @@ __global__ __launch_bounds__(256) void jg_round0_sum(JgSegs S, JgJ J, uint32_t n
 // 1.6 GB of q) and spends an ext x base product plus a table walk per element.
 struct JgTab { const uint32_t* q; uint32_t height, col0, ncols, tile0, x0, tile1, tile2; };   // q: the table's first column in the dense buffer; x0: its dense index; tile0/1/2: first tile in the round-0 / one-level / two-level fold launches
 constexpr uint32_t JG_TAB_PAIRS = 256;                                       // row pairs per tile
+constexpr uint32_t JG_COL_SLICE = 64;                                        // columns per table descriptor (see where the tables are listed)
 __global__ __launch_bounds__(256) void jg_round0_tables(const JgTab* __restrict__ tabs, uint32_t n_tabs, uint32_t n_tiles,
                                                         JgJ J, JgTail tail) {
     Ext e0 = kb::ext_zero(), eh = kb::ext_zero();
@@ -958,7 +959,7 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
     SP1HIP_REQUIRE(max_log_row_count >= 0 && max_log_row_count <= 30, "max_log_row_count out of range");
     hipStream_t s = S(stream);
     // SP1HIP_JG_TIMING=1: host wall time of the call's parts on stderr
-    const bool jg_timing = [] { const char* e = getenv("SP1HIP_JG_TIMING"); return e && e[0] == '1'; }();
+    const bool jg_timing = env_flag("SP1HIP_JG_TIMING", false);
     std::chrono::steady_clock::time_point jg_t[7];
     jg_t[0] = std::chrono::steady_clock::now();
     struct StageMarks {                                   // roctx sub-ranges of the evaluation proof (rocprofv3 --marker-trace)
@@ -1066,13 +1067,14 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
     DeviceBuf tabs[4];                 // q/j ping-pong: q of odd levels in tabs[0], of even levels in tabs[2]; j behind each
     const uint32_t n1 = (T + 1) / 2;
     // levels 1 .. rf keep J factored (see jg_foldf_sum): every column must start at a multiple of 2^level
+    const bool factored_enabled = env_flag("SP1HIP_JAGGED_FACTORED", true);     // A/B switch (tests)
     int rf = 0;
     {
         uint32_t g = T;
         for (uint32_t pfx : prefix) g |= pfx;
         rf = g ? __builtin_ctz(g) : 0;
         rf = std::min(rf, std::min(log_m - 2, max_log_row_count - 1));
-        if (const char* e = getenv("SP1HIP_JAGGED_FACTORED")) if (e[0] == '0') rf = 0;     // A/B switch
+        if (!factored_enabled) rf = 0;
         if (rf < 2) rf = 0;            // a single factored level is not worth the extra table
     }
     bool j_materialised = rf == 0;     // does tabs[cur + 1] hold the j table of the current level?
@@ -1113,8 +1115,7 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
     {
         uint32_t g = T;
         for (uint32_t pfx : prefix) g |= pfx;
-        const char* e = getenv("SP1HIP_JAGGED_FACTORED");
-        if ((g & 1u) == 0 && !(e && e[0] == '0')) {
+        if ((g & 1u) == 0 && factored_enabled) {
             uint64_t seg_start = 0;
             uint32_t col = 0;
             for (int r = 0; r < n_rounds; r++) {
@@ -1127,12 +1128,10 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
                         // a lane of the table-major kernels owns a few rows of a table and walks its columns one after the other, so a
                         // wide, short table is a few waves with a long dependent loop: the 2,640 columns x 122k rows of a Keccak shard
                         // made jg_fold_tables<2> one 3.3 ms launch on 60 workgroups (0.7 ms on a core shard of the same area). Every
-                        // quantity is a sum over columns, so a table enters as slices of at most `col_slice` columns — descriptors of
-                        // their own, the kernels see narrower tables. SP1HIP_JAGGED_COL_SLICE=0: whole tables (A/B; same bytes).
-                        static const uint32_t col_slice = [] { const char* e2 = getenv("SP1HIP_JAGGED_COL_SLICE"); return e2 ? (uint32_t)strtoul(e2, nullptr, 10) : 64u; }();
-                        const uint32_t step = col_slice ? col_slice : w;
-                        for (uint32_t c_lo = 0; c_lo < w; c_lo += step) {
-                            const uint32_t wc = std::min(step, w - c_lo);
+                        // quantity is a sum over columns, so a table enters as slices of at most JG_COL_SLICE columns — descriptors of
+                        // their own, the kernels see narrower tables.
+                        for (uint32_t c_lo = 0; c_lo < w; c_lo += JG_COL_SLICE) {
+                            const uint32_t wc = std::min(JG_COL_SLICE, w - c_lo);
                             const uint64_t o = off + (uint64_t)c_lo * h;
                             tabs0.push_back(JgTab{(const uint32_t*)d->d_dense + o, h, col + c_lo, wc, n_tiles0, (uint32_t)(seg_start + o), n_tiles1, n_tiles2});
                             n_tiles0 += (h / 2 + JG_TAB_PAIRS - 1) / JG_TAB_PAIRS;
@@ -1164,7 +1163,7 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
     int cur = 0;                       // tabs[cur] (and tabs[cur + 1] once materialised) hold (q, j) of the current level
     jg_t[1] = std::chrono::steady_clock::now();
     // SP1HIP_JAGGED_LOOKAHEAD=0: rounds 0 and 1 as two passes over the base words (the A/B form; the GPU tests run both)
-    const bool lookahead01 = skip_level1 && !tabs0.empty() && log_m >= 2 && !([] { const char* e = getenv("SP1HIP_JAGGED_LOOKAHEAD"); return e && e[0] == '0'; }());
+    const bool lookahead01 = skip_level1 && !tabs0.empty() && log_m >= 2 && env_flag("SP1HIP_JAGGED_LOOKAHEAD", true);
     for (int round = 0; round < log_m; round++) {
         uint32_t nb;
         if (round == 0 && lookahead01) {

@@ -159,7 +159,7 @@ int leaf_hash_part(const uint32_t* const* d_cols, uint32_t width, int k, int n_p
                    uint32_t* d_tree, const DeviceCtx* ctx, hipStream_t s) {
     ScopedTimer t("leaf_hash", s);
     // SP1HIP_LEAF_WGS=n: at most n workgroups (persistent grid); 0 / unset: one workgroup per 256 rows
-    const uint32_t cap = [] { const char* e = getenv("SP1HIP_LEAF_WGS"); return e ? (uint32_t)atoi(e) : 0u; }();
+    const uint32_t cap = (uint32_t)env_uint("SP1HIP_LEAF_WGS", 0);
     const uint32_t wgs = (height + 255) / 256;
     const dim3 grid(cap ? std::min(cap, wgs) : wgs), block(256);
     const bool first = k == 0, last = k == n_parts - 1;

@@ -183,11 +183,9 @@ extern "C" int sp1hip_rs_encode_batch(uint32_t* d_out, const uint32_t* d_in, int
     hipStream_t s = S(stream);
     const int lg_total = lg_n + lg_blowup;
     {
-        // large transforms: register-radix passes (ntt_fast.hip); SP1HIP_NTT_GENERIC=1 forces the
-        // generic LDS kernels below (kept for small sizes and as an A/B reference)
-        static const bool force_generic = getenv("SP1HIP_NTT_GENERIC") != nullptr;
+        // large transforms: register-radix passes (ntt_fast.hip); the generic LDS kernels below take the sizes outside its plan
         int bits[3], np;
-        if (!force_generic && ntt_fast_plan(lg_total, bits, &np))
+        if (ntt_fast_plan(lg_total, bits, &np))
             return ntt_fast_encode(d_out, d_in, lg_n, lg_blowup, n_cols, ctx, s);
     }
     const PassPlan plan = plan_passes(lg_total);

@@ -276,9 +276,6 @@ bool ntt_fast_plan(int lg_total, int bits[3], int* n_passes) {
     if (lg_total >= 18 && lg_total <= 24) {
         const int base = lg_total / 3, rem = lg_total % 3;
         for (int i = 0; i < 3; i++) bits[i] = base + (i >= 3 - rem ? 1 : 0);
-        if (const char* e = getenv("SP1HIP_NTT_PLAN")) {      // experiment: "877" etc.
-            if (strlen(e) == 3 && (e[0] - '0') + (e[1] - '0') + (e[2] - '0') == lg_total) for (int i = 0; i < 3; i++) bits[i] = e[i] - '0';
-        }
         *n_passes = 3;
         return true;
     }

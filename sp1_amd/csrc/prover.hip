@@ -580,9 +580,8 @@ int commit_mles_hooked(const sp1hip_tensor_t* mles, int n_mles, int lg_n, int lg
     SP1HIP_TRY(pd->tree.alloc((2 * N - 1) * 32, s));
     DeviceBuf rc;
     SP1HIP_TRY(rc.alloc(64, s));
-    const char* ov = getenv("SP1HIP_COMMIT_OVERLAP");
     // default: overlap when the codeword is large enough to fill the chip; "0" never, "1" always (tests)
-    const bool overlap = ov ? ov[0] != '0' : N * (size_t)pd->total_width >= ((size_t)1 << 24);
+    const bool overlap = env_flag("SP1HIP_COMMIT_OVERLAP", N * (size_t)pd->total_width >= ((size_t)1 << 24));
     std::vector<LeafPart> parts;
     if (overlap) leaf_hash_plan(pd->cw_tensors.data(), n_mles, &parts);
     if (parts.size() >= 2) {

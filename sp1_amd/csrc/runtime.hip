@@ -47,7 +47,7 @@ int ensure_dynamic_lds(const void* kernel, int bytes) {
     return SP1HIP_SUCCESS;
 }
 int wait_timeout_seconds() {
-    static const int t = [] { const char* e = getenv("SP1HIP_WAIT_TIMEOUT_S"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 60; }();
+    static const int t = [] { const uint64_t v = env_uint("SP1HIP_WAIT_TIMEOUT_S", 60); return v > 0 && v <= 0x7fffffffu ? (int)v : 60; }();
     return t;
 }
 
@@ -620,31 +620,6 @@ void mailbox_release(MailboxSlot slot) {
     g_mb_free[dev].push_back(slot);
 }
 
-static std::vector<HostGateBlock> g_gate_free[64];
-
-int host_gate_acquire(HostGateBlock* out) {
-    int dev = 0;
-    SP1HIP_HIP(hipGetDevice(&dev));
-    SP1HIP_REQUIRE(dev >= 0 && dev < 64, "device index out of range");
-    {
-        std::lock_guard<std::mutex> lock(g_rs_mutex);
-        if (!g_gate_free[dev].empty()) { *out = g_gate_free[dev].back(); g_gate_free[dev].pop_back(); return SP1HIP_SUCCESS; }
-    }
-    HostGateBlock b{nullptr};
-    const size_t words = 64 + (size_t)GATE_RING * GATE_SLOT_WORDS;
-    SP1HIP_HIP(hipHostMalloc((void**)&b.h, words * 4, hipHostMallocMapped));
-    memset(b.h, 0, words * 4);
-    *out = b;
-    return SP1HIP_SUCCESS;
-}
-
-void host_gate_release(HostGateBlock b) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return;
-    std::lock_guard<std::mutex> lock(g_rs_mutex);
-    g_gate_free[dev].push_back(b);
-}
-
 static std::vector<PinnedBlock> g_pin_free[64];
 
 int pinned_stage_acquire(PinnedBlock* out) {
@@ -678,8 +653,7 @@ struct RoctxApi {
     int (*push)(const char*) = nullptr;
     int (*pop)() = nullptr;
     RoctxApi() {
-        const char* e = getenv("SP1HIP_ROCTX");
-        if (e && e[0] == '0') return;
+        if (!env_flag("SP1HIP_ROCTX", true)) return;
         for (const char* lib : {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"}) {
             void* h = dlopen(lib, RTLD_NOW | RTLD_GLOBAL);
             if (!h) continue;

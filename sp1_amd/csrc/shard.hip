@@ -132,7 +132,7 @@ int sp1hip_prove_shard(const sp1hip_shard_chip_t* chips, int n_chips, const uint
     }
 
     // SP1HIP_SHARD_TIMING=1: host wall time of the stages on stderr
-    const bool sh_timing = [] { const char* e = getenv("SP1HIP_SHARD_TIMING"); return e && e[0] == '1'; }();
+    const bool sh_timing = env_flag("SP1HIP_SHARD_TIMING", false);
     std::chrono::steady_clock::time_point sh_t[6];
     sh_t[0] = std::chrono::steady_clock::now();
     // roctx ranges per stage (rocprofv3 --marker-trace): one open range at a time, closed on every exit path

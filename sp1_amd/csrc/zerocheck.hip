@@ -103,8 +103,11 @@ constexpr uint32_t ZC_CHUNK_HARD_MAX = 320; // a chunk may grow to this while it
 // ~ZC_FINE_LIMIT instructions with no regard for recomputation: more workgroups, each a third as long
 constexpr uint32_t ZC_FINE_LIMIT = 32, ZC_FINE_MAX_TERMS = 64;
 // rounds with at most this many workgroups (x 3 nodes) launch their groups / fused pieces on fork streams; the default forks every round
-// (the large rounds gain the overlap of one launch's tail with the next one's head). SP1HIP_ZC_FORK_MAX_BLOCKS overrides (A/B runs).
+// (the large rounds gain the overlap of one launch's tail with the next one's head).
 constexpr uint32_t ZC_FORK_MAX_BLOCKS = 1u << 30;
+// the interpreter's workgroups of one chunk cover at most this many row pairs (quads in the bivariate rounds) per pass: the blocks of a
+// taller chip stride over the rest
+constexpr uint32_t ZC_MAX_PAIRS = 131072;
 // rounds with at most this many workgroups are "small": every launch is at its latency floor (the two septic kinds then share one launch)
 constexpr uint32_t ZC_SMALL_ROUND_WGS = 16384;
 
@@ -390,7 +393,7 @@ template <bool FIRST, int MAXR, bool STAGED>
 __global__ __launch_bounds__(256) void zc_round_kernel(const ZcDesc* __restrict__ descs, int n_descs,
                                                        const uint32_t* __restrict__ eq, uint32_t eq_len,
                                                        const uint32_t* __restrict__ publics, uint32_t* __restrict__ partial,
-                                                       uint32_t rf_off, uint32_t block_base, uint32_t fused_flag) {
+                                                       uint32_t rf_off, uint32_t block_base) {
     using K = KT<FIRST>;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* red = lds;                                   // [4][8] reduction scratch
@@ -402,11 +405,10 @@ __global__ __launch_bounds__(256) void zc_round_kernel(const ZcDesc* __restrict_
     }
     if (threadIdx.x < 32) red[threadIdx.x] = 0;            // workgroups narrower than 4 waves leave slots untouched
     // The three nodes of a block of row pairs are three CONSECUTIVE workgroups: dispatched together (to different XCDs),
-    // their re-reads of the same table rows meet in the memory-side cache instead of HBM. `fused` (A/B knob
-    // SP1HIP_ZC_FUSE_NODES=1) makes one workgroup evaluate all three nodes instead; measured slower, see the host side.
-    const bool fused = (fused_flag != 0);
-    const uint32_t bid = block_base + (fused ? blockIdx.x : blockIdx.x / 3u);
-    const int only_pass = fused ? -1 : (int)(blockIdx.x % 3u);
+    // their re-reads of the same table rows meet in the memory-side cache instead of HBM (one workgroup evaluating
+    // all three nodes was measured slower, see the host side).
+    const uint32_t bid = block_base + blockIdx.x / 3u;
+    const int only_pass = (int)(blockIdx.x % 3u);
     const ZcDesc d = zc_find_desc(descs, n_descs, bid);
     if constexpr (STAGED) {
         const uint4* src = reinterpret_cast<const uint4*>(d.prog);
@@ -426,7 +428,7 @@ __global__ __launch_bounds__(256) void zc_round_kernel(const ZcDesc* __restrict_
         for (int k = 0; k < 4; k++) e.c[k] = eq[(size_t)k * eq_len + i];
 #pragma unroll
         for (int pass = 0; pass < 3; pass++) {
-            if (only_pass >= 0 && pass != only_pass) continue;
+            if (pass != only_pass) continue;
             kb::Ext va = kb::ext_zero(), vb = kb::ext_zero();
             if (FIRST && pass == 0) {
                 if (d.flags & 1u)
@@ -453,7 +455,7 @@ __global__ __launch_bounds__(256) void zc_round_kernel(const ZcDesc* __restrict_
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int pass = 0; pass < 3; pass++) {
-        if (only_pass >= 0 && pass != only_pass) continue;
+        if (pass != only_pass) continue;
         uint32_t v[8];
 #pragma unroll
         for (int k = 0; k < 4; k++) { v[k] = sa[pass].c[k]; v[4 + k] = sb[pass].c[k]; }
@@ -548,15 +550,13 @@ __global__ __launch_bounds__(256) void zc_macro_kernel(const ZcDesc* __restrict_
 
 // ---- bivariate kernels. Interpreter: blockIdx.x = 3 b + g -> (block b of `block_pairs` row QUADS of one chunk, node group g =
 // nodes 4 g .. 4 g + 3, four node values per register: KT4). A node's slot is [A | B] like the single-round kernels': A = sum eq
-// C(node e); B = the GKR batching term's corner sum (X, Y) = (e >> 1, e & 1) for e < 4 from the chip's first chunk (zero
-// elsewhere). partial[(12 bid + e) * 8 ..).
+// C(node e); B = 0 here (the GKR batching term's corner sums come from zc_biv_corner_kernel's slots). partial[(12 bid + e) * 8 ..).
 constexpr uint32_t ZC_BIV_GROUPS = 3;
 template <int MAXR, bool STAGED>
 __global__ __launch_bounds__(256) void zc_biv_round_kernel(const ZcDesc* __restrict__ descs, int n_descs,
                                                            const uint32_t* __restrict__ eq, uint32_t eq_len,
                                                            const uint32_t* __restrict__ publics, uint32_t* __restrict__ partial,
                                                            uint32_t rf_off, uint32_t block_base) {
-    using K = KT<true>;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* red = lds;                                   // [4][8] reduction scratch
     uint4* lprog = reinterpret_cast<uint4*>(lds + 32);
@@ -575,10 +575,9 @@ __global__ __launch_bounds__(256) void zc_biv_round_kernel(const ZcDesc* __restr
     }
     __syncthreads();
     const uint32_t quads = (d.rows + 3) / 4;
-    const bool corners = grp == 0 && (d.flags & 1u);
-    kb::Ext sa[4], sb[4];
+    kb::Ext sa[4];
 #pragma unroll
-    for (int n = 0; n < 4; n++) { sa[n] = kb::ext_zero(); sb[n] = kb::ext_zero(); }
+    for (int n = 0; n < 4; n++) sa[n] = kb::ext_zero();
     for (uint32_t base = (bid - d.block_start) * d.block_pairs; base < quads; base += d.n_blocks * d.block_pairs)
     for (uint32_t i = base + threadIdx.x; i < min(base + d.block_pairs, quads); i += blockDim.x) {
         kb::Ext e;
@@ -589,35 +588,20 @@ __global__ __launch_bounds__(256) void zc_biv_round_kernel(const ZcDesc* __restr
         else (void)run_program<true, MAXR, true>(reg, (zc_const_prog_t)(uintptr_t)d.prog, d, publics, i, (int)grp, false, va);
 #pragma unroll
         for (int n = 0; n < 4; n++) sa[n] = kb::ext_add(sa[n], kb::ext_mul(va[n], e));
-        if (corners) {                                      // row 4 i + n of every column, weighted by the GKR powers
-            kb::Ext vb[4] = {kb::ext_zero(), kb::ext_zero(), kb::ext_zero(), kb::ext_zero()};
-            for (uint32_t c = 0; c < d.main_w + d.prep_w; c++) {
-                const kb::Ext pw = load_ext_aos(d.gkr_pows, c);
-                const uint32_t* tbl = c < d.main_w ? d.main : d.prep;
-                const uint32_t col = c < d.main_w ? c : c - d.main_w;
-#pragma unroll
-                for (uint32_t n = 0; n < 4; n++)
-                    if (4 * i + n < d.rows) vb[n] = kb::ext_add(vb[n], K::scale(pw, K::load(tbl, col, d.rows, 4 * i + n)));
-            }
-#pragma unroll
-            for (int n = 0; n < 4; n++) sb[n] = kb::ext_add(sb[n], kb::ext_mul(vb[n], e));
-        }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int n = 0; n < 4; n++) {
-        uint32_t v[8];
+        uint32_t v[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) { v[k] = sa[n].c[k]; v[4 + k] = sb[n].c[k]; }
-#pragma unroll
-        for (int k = 0; k < 8; k++) v[k] = zc_wave_sum(v[k]);
+        for (int k = 0; k < 4; k++) v[k] = zc_wave_sum(sa[n].c[k]);
         __syncthreads();
         if (lane == 0) {
 #pragma unroll
-            for (int k = 0; k < 8; k++) red[wave * 8 + k] = v[k];
+            for (int k = 0; k < 4; k++) red[wave * 8 + k] = v[k];
         }
         __syncthreads();
-        if (threadIdx.x < 8) {
+        if (threadIdx.x < 8) {                             // (words 4..7 of `red` stay zero: the B half)
             const uint32_t k = threadIdx.x;
             partial[((size_t)bid * ZC_BIV_NODES + 4 * grp + n) * 8 + k] = kb::add(kb::add(red[k], red[8 + k]), kb::add(red[16 + k], red[24 + k]));
         }
@@ -1036,85 +1020,6 @@ __global__ __launch_bounds__(256) void zc_biv_poly_kernel(const ZcDesc* __restri
         for (uint32_t w = 1; w < blockDim.x / 64; w++) acc = kb::add(acc, red[w * 48 + k]);
         partial[((size_t)bid * ZC_BIV_NODES + k / 4) * 8 + (k & 3u)] = acc;
         partial[((size_t)bid * ZC_BIV_NODES + k / 4) * 8 + 4 + (k & 3u)] = 0u;
-    }
-}
-
-// The Keccak pieces in the extension rounds, the THREE nodes of a row pair per pass (SP1HIP_ZC_KECCAK3=1; off by default, see below): the pieces are
-// bound by the bandwidth of their column loads, and one node per workgroup reads both rows of every column three times. Here a
-// lane loads the two rows once and carries the values at t = 0, 2, 4 through the piece (element-wise arithmetic on three extension
-// values: 12 VGPRs per live value). blockIdx.x = block; partial slots of the three nodes as the per-node kernels write them.
-// Measured (round 5, precompile shard): 250 VGPRs, two waves per SIMD, zerocheck rounds 31.0 ms against 22.0 ms for one node per
-// workgroup -- the saved loads do not pay for the lost occupancy, so the per-node kernels stay the default.
-struct E3 { kb::Ext n[3]; };
-struct P2Ext3 {
-    using T = E3;
-    static __device__ __forceinline__ T add(const T& a, const T& b) { return T{{kb::ext_add(a.n[0], b.n[0]), kb::ext_add(a.n[1], b.n[1]), kb::ext_add(a.n[2], b.n[2])}}; }
-    static __device__ __forceinline__ T sub(const T& a, const T& b) { return T{{kb::ext_sub(a.n[0], b.n[0]), kb::ext_sub(a.n[1], b.n[1]), kb::ext_sub(a.n[2], b.n[2])}}; }
-    static __device__ __forceinline__ T mul(const T& a, const T& b) { return T{{kb::ext_mul(a.n[0], b.n[0]), kb::ext_mul(a.n[1], b.n[1]), kb::ext_mul(a.n[2], b.n[2])}}; }
-    static __device__ __forceinline__ T addc(T a, uint32_t c) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) a.n[k].c[0] = kb::add(a.n[k].c[0], c);
-        return a;
-    }
-    static __device__ __forceinline__ T mulc(const T& a, uint32_t c) { return T{{kb::ext_mul_base(a.n[0], c), kb::ext_mul_base(a.n[1], c), kb::ext_mul_base(a.n[2], c)}}; }
-};
-__global__ __launch_bounds__(256) void zc_keccak3_kernel(const ZcDesc* __restrict__ descs, int n_descs, const uint32_t* __restrict__ eq,
-                                                         uint32_t eq_len, uint32_t* __restrict__ partial, uint32_t block_base) {
-    using K = KT<false>;
-    __shared__ uint32_t red[4][24];
-    const uint32_t bid = block_base + blockIdx.x;
-    const ZcDesc d = zc_find_desc(descs, n_descs, bid);
-    const uint32_t q = (d.flags >> 8) & 15u, base_col = d.pad;
-    const uint32_t terms = (d.rows + 1) / 2;
-    kb::Ext sa[3] = {kb::ext_zero(), kb::ext_zero(), kb::ext_zero()}, sb[2] = {kb::ext_zero(), kb::ext_zero()};
-    for (uint32_t base = (bid - d.block_start) * d.block_pairs; base < terms; base += d.n_blocks * d.block_pairs)
-    for (uint32_t i = base + threadIdx.x; i < min(base + d.block_pairs, terms); i += blockDim.x) {
-        kb::Ext e;
-#pragma unroll
-        for (int k = 0; k < 4; k++) e.c[k] = eq[(size_t)k * eq_len + i];
-        kb::Ext va[3] = {kb::ext_zero(), kb::ext_zero(), kb::ext_zero()}, vb[2] = {kb::ext_zero(), kb::ext_zero()};
-        const bool odd = 2 * i + 1 < d.rows;
-        auto ld = [&](uint32_t c, bool owned) -> E3 {
-            const uint32_t col = base_col + c;
-            const kb::Ext r0 = K::load(d.main, col, d.rows, 2 * i);
-            const kb::Ext r1 = odd ? K::load(d.main, col, d.rows, 2 * i + 1) : kb::ext_zero();
-            const kb::Ext slope = kb::ext_sub(r1, r0), s2 = kb::ext_add(slope, slope);
-            E3 v;
-            v.n[0] = r0;
-            v.n[1] = kb::ext_add(s2, r0);
-            v.n[2] = kb::ext_add(kb::ext_add(s2, s2), r0);
-            if (owned) {                                   // the GKR-opening batching term at nodes 0 and 2 (g(4) = 2 g(2) - g(0))
-                const kb::Ext pw = load_ext_aos(d.gkr_pows, col);
-                vb[0] = kb::ext_add(vb[0], kb::ext_mul(v.n[0], pw));
-                vb[1] = kb::ext_add(vb[1], kb::ext_mul(v.n[1], pw));
-            }
-            return v;
-        };
-        auto sink = [&](uint32_t j, const E3& v) {
-            const kb::Ext a = load_ext_aos(d.alpha_pows, d.alpha_off + j);
-#pragma unroll
-            for (int n = 0; n < 3; n++) va[n] = kb::ext_add(va[n], kb::ext_mul(v.n[n], a));
-        };
-        zc_keccak_piece<P2Ext3>(q, ld, sink);
-#pragma unroll
-        for (int n = 0; n < 3; n++) sa[n] = kb::ext_add(sa[n], kb::ext_mul(va[n], e));
-#pragma unroll
-        for (int n = 0; n < 2; n++) sb[n] = kb::ext_add(sb[n], kb::ext_mul(vb[n], e));
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // words: pass p -> [A_p (4) | B_p (4)], B_2 = 0
-#pragma unroll
-    for (int p = 0; p < 3; p++)
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t w = k < 4 ? sa[p].c[k] : (p < 2 ? sb[p].c[k - 4] : 0u);
-            const uint32_t v = zc_wave_sum(w);
-            if (lane == 0) red[wave][p * 8 + k] = v;
-        }
-    __syncthreads();
-    if (threadIdx.x < 24) {
-        const uint32_t w = threadIdx.x;
-        partial[(size_t)bid * 24 + w] = kb::add(kb::add(red[0][w], red[1][w]), kb::add(red[2][w], red[3][w]));
     }
 }
 
@@ -1637,24 +1542,21 @@ static int allocate_registers(const uint32_t* ssa, uint32_t n, std::vector<uint3
     // it is not emitted, its user becomes a MADC
     std::vector<char> fused(n, 0);
     std::vector<int> fused_src(n, -1);         // for the user: the MULC it absorbs
-    static const bool madc_enabled = [] { const char* e = getenv("SP1HIP_ZC_MADC"); return !(e && e[0] == '0'); }();
-    static const bool mad_enabled = [] { const char* e = getenv("SP1HIP_ZC_MAD"); return !(e && e[0] == '0'); }();
-    if (madc_enabled || mad_enabled)
-        for (uint32_t k = 0; k + 1 < n; k++) {
-            const bool is_mulc = ssa[3 * k] == ZC_MULC && madc_enabled;
-            const bool is_mul = ssa[3 * k] == ZC_MUL && mad_enabled && ssa[3 * k + 1] != ssa[3 * k + 2];
-            if (!(is_mulc || is_mul) || n_uses[k] != 1) continue;
-            uint32_t u = k + 1;
-            while (u < n && ssa[3 * u] == ZC_ASSERT_ZERO) u++;
-            if (u >= n || fused_src[u] >= 0) continue;
-            const uint32_t uop = ssa[3 * u], ua = ssa[3 * u + 1], ub = ssa[3 * u + 2];
-            if (ua == ub) continue;
-            if (is_mul) {                      // the other summand must not be one of the factors (it may live in `prev` only)
-                const uint32_t other = ua == k ? ub : ua;
-                if (other == ssa[3 * k + 1] || other == ssa[3 * k + 2]) continue;
-            }
-            if ((uop == ZC_ADD && (ua == k || ub == k)) || (uop == ZC_SUB && ub == k)) { fused[k] = 1; fused_src[u] = (int)k; }
+    for (uint32_t k = 0; k + 1 < n; k++) {
+        const bool is_mulc = ssa[3 * k] == ZC_MULC;
+        const bool is_mul = ssa[3 * k] == ZC_MUL && ssa[3 * k + 1] != ssa[3 * k + 2];
+        if (!(is_mulc || is_mul) || n_uses[k] != 1) continue;
+        uint32_t u = k + 1;
+        while (u < n && ssa[3 * u] == ZC_ASSERT_ZERO) u++;
+        if (u >= n || fused_src[u] >= 0) continue;
+        const uint32_t uop = ssa[3 * u], ua = ssa[3 * u + 1], ub = ssa[3 * u + 2];
+        if (ua == ub) continue;
+        if (is_mul) {                      // the other summand must not be one of the factors (it may live in `prev` only)
+            const uint32_t other = ua == k ? ub : ua;
+            if (other == ssa[3 * k + 1] || other == ssa[3 * k + 2]) continue;
         }
+        if ((uop == ZC_ADD && (ua == k || ub == k)) || (uop == ZC_SUB && ub == k)) { fused[k] = 1; fused_src[u] = (int)k; }
+    }
     {   // next_val[k]: the first value-producing (emitted) instruction after k
         int nv = -1;
         for (uint32_t k = n; k-- > 0;) { next_val[k] = nv; if (ssa[3 * k] != ZC_ASSERT_ZERO && !fused[k]) nv = (int)k; }
@@ -1999,8 +1901,9 @@ static int zc_get_plan(const uint32_t* program, uint32_t n_instr, uint32_t main_
     uint64_t h = 1469598103934665603ull;
     auto mix = [&](uint32_t v) { h = (h ^ v) * 1099511628211ull; };
     // SP1HIP_ZC_MACRO=0 ignores hints; read per call like the BIVARIATE / FORK switches and part of the cache key
-    const bool macros_enabled = [] { const char* e = getenv("SP1HIP_ZC_MACRO"); return !(e && e[0] == '0'); }();
-    const uint64_t mul_min_rows = [] { const char* e = getenv("SP1HIP_ZC_MUL_MIN_ROWS"); return e ? (uint64_t)strtoull(e, nullptr, 10) : ZC_MUL_MIN_ROWS; }();
+    const bool macros_enabled = env_flag("SP1HIP_ZC_MACRO", true);
+    const uint64_t mul_min_rows = env_uint("SP1HIP_ZC_MUL_MIN_ROWS", ZC_MUL_MIN_ROWS);
+    static const bool zc_debug = env_flag("SP1HIP_ZC_DEBUG", false);
     const bool mul_enabled = macros_enabled && rows >= mul_min_rows;
     mix(main_width); mix(prep_width); mix(n_instr); mix((macros_enabled ? 1u : 0u) | (mul_enabled ? 2u : 0u));
     for (size_t k = 0; k < (size_t)n_instr * 3; k++) mix(program[k]);
@@ -2065,7 +1968,7 @@ static int zc_get_plan(const uint32_t* program, uint32_t n_instr, uint32_t main_
                         m.aux0 = (uint32_t)np->polys.size(); m.n_c = n_c;
                         np->polys.push_back(std::move(poly));
                         np->macros.push_back(m);
-                    } else if (getenv("SP1HIP_ZC_DEBUG")) {
+                    } else if (zc_debug) {
                         fprintf(stderr, "[sp1hip zc] chip %d: polynomial-identity hint at constraint %u dropped (a named value is not affine in the main columns)\n", chip_index, asserts_before);
                     }
                     k = j - 1;
@@ -2147,18 +2050,15 @@ static int zc_get_plan(const uint32_t* program, uint32_t n_instr, uint32_t main_
         // fold constants into immediates, then pick the instruction order with the smallest register file
         std::vector<uint32_t> folded, sched;
         fold_immediates(program, n_instr, &folded);
-        static const int forced_mode = [] { const char* e = getenv("SP1HIP_ZC_SCHEDULE"); return e ? atoi(e) : -1; }();
-        SP1HIP_REQUIRE(forced_mode <= 3, "SP1HIP_ZC_SCHEDULE must be 0, 1, 2 or 3 (a debug knob; unset = try them)");
         // mode 3 (rematerialised loads: a ~3x longer program with a much smaller file) only where the file is the problem: when the
-        // best of the other orders needs at least this many registers (SP1HIP_ZC_LAZY_MIN_REGS; 64 = two waves' files per CU). It was
+        // best of the other orders needs at least ZC_LAZY_MIN_REGS registers (64 = two waves' files per CU). It was
         // 128 while the secp256k1 / uint256 chips (195 - 225) were the only ones above 40; the tower / carry chips that came later
         // (Bn254FpOpAssign 103, Uint256Ops 71, Bn254Fp2AddSubAssign 66: the same FieldOpCols programs) take the same form at 64;
         // every chip with a measured schedule is below 40 and keeps it
-        static const uint32_t lazy_min_regs = [] { const char* e = getenv("SP1HIP_ZC_LAZY_MIN_REGS"); return e ? (uint32_t)strtoul(e, nullptr, 10) : 64u; }();
+        constexpr uint32_t ZC_LAZY_MIN_REGS = 64;
         uint32_t best_regs = 0xffffffffu;
         for (int mode = 0; mode < 4; mode++) {
-            if (forced_mode >= 0 && mode != forced_mode) continue;
-            if (forced_mode < 0 && mode == 3 && best_regs < lazy_min_regs) continue;
+            if (mode == 3 && best_regs < ZC_LAZY_MIN_REGS) continue;
             std::vector<uint32_t> cand;
             std::vector<Chunk> mono;
             schedule_program(folded.data(), n_instr, main_width, mode, &cand);
@@ -2170,7 +2070,6 @@ static int zc_get_plan(const uint32_t* program, uint32_t n_instr, uint32_t main_
             if (regs < best_regs) { best_regs = regs; sched.swap(cand); np->mono.swap(mono); }
         }
         const uint32_t n_sched = (uint32_t)(sched.size() / 3);
-        static const bool zc_debug = getenv("SP1HIP_ZC_DEBUG") != nullptr;
         if (zc_debug) {
             size_t mono_instr = 0;
             for (auto& ck : np->mono) mono_instr += ck.prog.size() / 4;
@@ -2178,11 +2077,9 @@ static int zc_get_plan(const uint32_t* program, uint32_t n_instr, uint32_t main_
                     chip_index, n_instr, main_width, prep_width, mono_instr, best_regs);
         }
         SP1HIP_TRY(allocate_registers(sched.data(), n_sched, &np->prog, &np->n_regs));
-        static const uint32_t chunk_limit = [] { const char* e = getenv("SP1HIP_ZC_CHUNK_LIMIT"); return e ? std::max<uint32_t>((uint32_t)atoi(e), 8u) : ZC_CHUNK_LIMIT; }();
-        static const uint32_t chunk_hard = [] { const char* e = getenv("SP1HIP_ZC_CHUNK_HARD_MAX"); return e ? std::max<uint32_t>((uint32_t)atoi(e), 8u) : ZC_CHUNK_HARD_MAX; }();
         std::vector<uint32_t> sched_f = sched;
         drop_hinted(sched_f);
-        SP1HIP_TRY(build_chunks(sched_f.data(), n_sched, main_width, prep_width, chunk_limit, &np->chunks, chunk_hard, &np->macros, &np->polys));
+        SP1HIP_TRY(build_chunks(sched_f.data(), n_sched, main_width, prep_width, ZC_CHUNK_LIMIT, &np->chunks, ZC_CHUNK_HARD_MAX, &np->macros, &np->polys));
         SP1HIP_TRY(build_chunks(sched_f.data(), n_sched, main_width, prep_width, ZC_FINE_LIMIT, &np->fine, ZC_FINE_LIMIT, &np->macros, &np->polys));
         np->sched = sched;
         // trust, but verify: on a pseudo-random row the fused pieces must give what the caller's SSA gives for the constraints
@@ -2232,14 +2129,9 @@ constexpr size_t ZC_LDS_BUDGET = ZC_LDS_CU;
 // workgroups = 192 lanes against one 128-lane workgroup). Ties go to the wider workgroup. 0 if even one wave's file does not
 // fit 160 KB (R > 160 in the extension rounds): the caller then runs the chip's finer chunks.
 template <bool FIRST> static inline uint32_t zc_wg_for(uint32_t n_regs, size_t other_lds) {
-    // Default (end of round 5): the occupancy rule above — the workgroup width that puts the most lanes on a CU. SP1HIP_ZC_WG=legacy:
-    // the widest workgroup whose file fits 64 KB (the rule every measurement of rounds 2-4 was taken with), the occupancy rule
-    // only for files beyond that. Measured with two fork streams: fibonacci shard 86.4-86.8 either way, recorded-shape shard
-    // 74.7 -> 74.2-74.6 (a 15-register program runs 640 lanes per CU instead of 512, a 7-register one 2,048 instead of 1,280)
-    const bool occ = [] { const char* e = getenv("SP1HIP_ZC_WG"); return !(e && e[0] == 'l'); }();     // default: occupancy; "legacy": the 64 KB rule
-    if (!occ)
-        for (uint32_t wg = 256; wg >= 64; wg >>= 1)
-            if (other_lds + zc_rf_lane_bytes<FIRST>(n_regs) * wg <= 64 * 1024) return wg;
+    // Measured (end of round 5, two fork streams) against the widest workgroup whose file fits 64 KB, the rule of rounds 2-4:
+    // fibonacci shard 86.4-86.8 either way, recorded-shape shard 74.7 -> 74.2-74.6 (a 15-register program runs 640 lanes per CU
+    // instead of 512, a 7-register one 2,048 instead of 1,280)
     uint32_t best = 0, best_lanes = 0;
     for (uint32_t wg = 256; wg >= 64; wg >>= 1) {
         const size_t per_wg = other_lds + zc_rf_lane_bytes<FIRST>(n_regs) * wg;
@@ -2252,22 +2144,21 @@ template <bool FIRST> static inline uint32_t zc_wg_for(uint32_t n_regs, size_t o
 
 // One group of descriptors = a contiguous block range [block_lo, block_lo + n_blocks) launched together.
 template <bool FIRST>
-static int launch_round(uint32_t max_regs, bool staged, bool fused, const ZcDesc* d_descs, int n_descs, uint32_t block_lo, uint32_t n_blocks,
+static int launch_round(uint32_t max_regs, bool staged, const ZcDesc* d_descs, int n_descs, uint32_t block_lo, uint32_t n_blocks,
                         uint32_t max_instr, const uint32_t* eq, uint32_t eq_len, const uint32_t* publics, uint32_t* partial, hipStream_t s) {
     const size_t lds = 32 * 4 + (staged ? (size_t)max_instr * 16 : 0);
-    dim3 grid(fused ? n_blocks : n_blocks * 3);      // unfused: workgroup 3 b + p = node p of block b
-    const uint32_t ff = fused ? 1u : 0u;
+    const dim3 grid(n_blocks * 3);                   // workgroup 3 b + p = node p of block b
     const uint32_t wg = zc_wg_for<FIRST>(max_regs, lds);
     SP1HIP_REQUIRE(wg != 0, "internal: a register file that does not fit LDS reached the launch (plan_round cuts such programs finer)");
     const size_t total = lds + zc_rf_lane_bytes<FIRST>(max_regs) * wg;
     if (staged) {
         auto kern = zc_round_kernel<FIRST, 0, true>;
         if (total > 48 * 1024) SP1HIP_TRY(ensure_dynamic_lds((const void*)kern, (int)ZC_LDS_BUDGET));
-        hipLaunchKernelGGL(kern, grid, dim3(wg), total, s, d_descs, n_descs, eq, eq_len, publics, partial, (uint32_t)(lds / 4), block_lo, ff);
+        hipLaunchKernelGGL(kern, grid, dim3(wg), total, s, d_descs, n_descs, eq, eq_len, publics, partial, (uint32_t)(lds / 4), block_lo);
     } else {
         auto kern = zc_round_kernel<FIRST, 0, false>;
         if (total > 48 * 1024) SP1HIP_TRY(ensure_dynamic_lds((const void*)kern, (int)ZC_LDS_BUDGET));
-        hipLaunchKernelGGL(kern, grid, dim3(wg), total, s, d_descs, n_descs, eq, eq_len, publics, partial, (uint32_t)(lds / 4), block_lo, ff);
+        hipLaunchKernelGGL(kern, grid, dim3(wg), total, s, d_descs, n_descs, eq, eq_len, publics, partial, (uint32_t)(lds / 4), block_lo);
     }
     SP1HIP_LAUNCH_CHECK();
     return SP1HIP_SUCCESS;
@@ -2316,14 +2207,11 @@ static int launch_biv_round(uint32_t max_regs, bool staged, const ZcDesc* d_desc
 int eq_prefix_tables_soa_async(const kb::Ext* h_point, int d, uint32_t* d_out, hipStream_t s);
 }
 
-// fork streams a round's launches are spread over, besides the caller's own (SP1HIP_ZC_NFORK = 1..3). Default 2 since the end of
+// fork streams a round's launches are spread over, besides the caller's own. Two since the end of
 // round 5: with three (+ the caller's = the four hardware queues a process gets) the commit's side stream shares a queue with one of
 // them; measured A/B/A/B on one box, whole proof: fibonacci shard 89.2 -> 86.4-86.8 ms, recorded-shape shard 76.8 -> 74.7 (one
 // fork: 88.0 / —)
-static int zc_fork_streams() {
-    static const int n = [] { const char* e = getenv("SP1HIP_ZC_NFORK"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : v > 3 ? 3 : v; }();
-    return n;
-}
+constexpr int ZC_N_FORK = 2;
 
 static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int max_log_row_count,
                                const sp1hip_ext_t* h_zeta, const sp1hip_ext_t* h_openings, sp1hip_ext_t alpha_c,
@@ -2355,7 +2243,7 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
     const DeviceCtx* ctx;
     SP1HIP_TRY(get_device_ctx(&ctx));
     // SP1HIP_ZC_TIMING=1: host wall time of the call's three parts on stderr (set-up before the first round | rounds | proof)
-    const bool zc_timing = [] { const char* e = getenv("SP1HIP_ZC_TIMING"); return e && e[0] == '1'; }();
+    const bool zc_timing = env_flag("SP1HIP_ZC_TIMING", false);
     const auto zc_t0 = std::chrono::steady_clock::now();
     auto zc_t1 = zc_t0, zc_t2 = zc_t0;
     const Ext alpha{{alpha_c.c[0], alpha_c.c[1], alpha_c.c[2], alpha_c.c[3]}};
@@ -2638,9 +2526,6 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
         std::vector<ZcChipRange>& ranges = rp.ranges;
         std::vector<int>& desc_chip = rp.desc_chip;
         std::vector<Group>& groups = rp.groups;
-        static const bool mono_enabled = [] { const char* e = getenv("SP1HIP_ZC_MONO"); return !(e && e[0] == '0'); }();
-        // SP1HIP_ZC_BIV_CORNERS=inline: the corner sums inside the interpreter's first chunk, as in rounds 4-5 (A/B runs; same bytes)
-        static const bool corner_kernel = [] { const char* e = getenv("SP1HIP_ZC_BIV_CORNERS"); return !(e && e[0] == 'i'); }();
         std::vector<char> use_mono(n_chips, 0);
         for (int i = 0; i < n_chips; i++) {
             ChipState& c = *st[i];
@@ -2658,9 +2543,8 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
             // (a shorter undivided program with the same register file is NOT enough: measured on the term-major Poseidon2
             // program — 2,804 words undivided against 3,808 in 28 chunks, 20 registers either way — the undivided form is
             // 36 % slower: 45 KB of instruction words stream through a 16 KB scalar cache, a chunk's 2-5 KB stay in it)
-            use_mono[i] = mono_enabled && c.chunks.size() > 1 && terms >= ZC_MONO_MIN_TERMS && mono_wg != 0 && 2 * chunk_words > 3 * mono_words;
-            static const bool fine_enabled = [] { const char* e = getenv("SP1HIP_ZC_FINE"); return !(e && e[0] == '0'); }();
-            if (!use_mono[i] && fine_enabled && terms <= ZC_FINE_MAX_TERMS && c.fine.size() > c.chunks.size()) use_mono[i] = 2;
+            use_mono[i] = c.chunks.size() > 1 && terms >= ZC_MONO_MIN_TERMS && mono_wg != 0 && 2 * chunk_words > 3 * mono_words;
+            if (!use_mono[i] && terms <= ZC_FINE_MAX_TERMS && c.fine.size() > c.chunks.size()) use_mono[i] = 2;
             const std::vector<Chunk>& cks = use_mono[i] == 1 ? c.mono : use_mono[i] == 2 ? c.fine : c.chunks;
             uint32_t regs = 1, instr = 1;
             for (auto& ck : cks) { regs = std::max(regs, ck.n_regs); instr = std::max<uint32_t>(instr, (uint32_t)(ck.prog.size() / 4)); }
@@ -2668,7 +2552,7 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
             // v_readfirstlane per instruction word, and the whole LDS budget goes to the register file). Staging programs
             // of up to SP1HIP_ZC_STAGE_MAX instructions in LDS instead was the default until it was measured 3-5 % slower
             // (recursion shard 14.6 vs 13.8 ms of round kernels, core-shaped 10.4 vs 10.1); the VGPR / scratch tier still stages.
-            const uint32_t stage_max = [] { const char* e = getenv("SP1HIP_ZC_STAGE_MAX"); return e ? (uint32_t)atoi(e) : 0u; }();   // read per call (tests)
+            const uint32_t stage_max = (uint32_t)env_uint("SP1HIP_ZC_STAGE_MAX", 0);   // read per call (tests)
             bool staged = instr <= stage_max;
             uint32_t wg = (r == 0 && !biv) ? zc_wg_for<true>(regs, staged ? 128 + (size_t)instr * 16 : 128) : zc_wg_for<false>(regs, staged ? 128 + (size_t)instr * 16 : 128);
             if (wg == 0 && use_mono[i] != 2) {      // the file does not fit LDS even for one wave: the finest cut of the program
@@ -2684,10 +2568,8 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
             // launch, and SyscallInstrs (32 rows, 23 registers) held the Add / Addi / Sub / Addw chips (7 registers, 4.5 million
             // rows of a fibonacci shard) to 3 workgroups of 128 lanes per CU where their own files allow 11. Chips too short for
             // occupancy to matter (the rounds that run the fine cut) share one group per width whatever their files.
-            // SP1HIP_ZC_GROUPS=legacy: one group per width (A/B runs; the proof bytes are the same).
-            static const bool by_residency = [] { const char* e = getenv("SP1HIP_ZC_GROUPS"); return !(e && e[0] == 'l'); }();
             uint32_t resident = 0;
-            if (by_residency && terms > ZC_FINE_MAX_TERMS) {
+            if (terms > ZC_FINE_MAX_TERMS) {
                 const size_t per_wg = (staged ? 128 + (size_t)instr * 16 : 128) + ((r == 0 && !biv) ? zc_rf_lane_bytes<true>(regs) : zc_rf_lane_bytes<false>(regs)) * wg;
                 resident = (uint32_t)std::min<size_t>(ZC_LDS_CU / per_wg, 2048 / wg);
             }
@@ -2707,8 +2589,7 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
                 const uint32_t terms = (uint32_t)((vrows[i] + unit - 1) / unit);
                 const uint32_t bp = g.wg ? g.wg : 256u;
                 uint32_t blocks = (terms + bp - 1) / bp;
-                static const uint32_t max_pairs = [] { const char* e = getenv("SP1HIP_ZC_MAX_PAIRS"); return e ? std::max<uint32_t>((uint32_t)atoi(e), 256u) : 131072u; }();
-                if (blocks > max_pairs / bp) blocks = std::max(1u, max_pairs / bp);
+                if (blocks > ZC_MAX_PAIRS / bp) blocks = std::max(1u, ZC_MAX_PAIRS / bp);
                 const std::vector<Chunk>& cks = use_mono[i] == 1 ? c.mono : use_mono[i] == 2 ? c.fine : c.chunks;
                 const std::vector<uint32_t>& offs = use_mono[i] == 1 ? c.mono_off : use_mono[i] == 2 ? c.fine_off : c.chunk_off;
                 ZcChipRange rg{total_blocks, 0, biv ? (uint32_t)(vrows[i] / 4) : terms - 1, 0};
@@ -2719,7 +2600,7 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
                     d.main = vmain[i]; d.prep = vprep[i]; d.main_w = c.in->main_width; d.prep_w = c.in->prep_width;
                     d.rows = (uint32_t)vrows[i]; d.alpha_pows = c.p_alpha; d.gkr_pows = c.p_gkr;
                     d.block_start = total_blocks; d.n_blocks = blocks;
-                    d.alpha_off = cks[q].alpha_off; d.flags = (q == 0 && !(biv && corner_kernel)) ? 1u : 0u;
+                    d.alpha_off = cks[q].alpha_off; d.flags = (q == 0 && !biv) ? 1u : 0u;
                     d.block_pairs = bp;
                     total_blocks += blocks;
                     descs.push_back(d);
@@ -2735,13 +2616,12 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
         uint32_t (&macro_lo)[ZC_MACRO_KINDS + 1] = rp.macro_lo;
         uint32_t (&macro_n)[ZC_MACRO_KINDS + 1] = rp.macro_n;
         // the polynomial identities: one lane per row pair while the round is large, one wave per pair once the tallest chip that has
-        // them is down to ZC_POLY_WAVE_MAX_TERMS pairs (SP1HIP_ZC_POLY_WAVE=0: always the former; same bytes)
+        // them is down to ZC_POLY_WAVE_MAX_TERMS pairs
         {
-            static const bool wave_on = [] { const char* e = getenv("SP1HIP_ZC_POLY_WAVE"); return !(e && e[0] == '0'); }();
             uint64_t max_terms = 0;
             for (int i = 0; i < n_chips; i++)
                 for (const ZcMacro& m : st[i]->macros) if (m.kind == ZC_HINT_POLY && vrows[i]) max_terms = std::max<uint64_t>(max_terms, (vrows[i] + unit - 1) / unit);
-            rp.poly_wave = wave_on && !biv && r > 0 && max_terms > 0 && max_terms <= ZC_POLY_WAVE_MAX_TERMS;
+            rp.poly_wave = !biv && r > 0 && max_terms > 0 && max_terms <= ZC_POLY_WAVE_MAX_TERMS;
         }
         for (uint32_t kind = ZC_HINT_POSEIDON2; kind < ZC_MACRO_KINDS; kind++) {
             if (kind == ZC_MACRO_BOTH_SEPTIC) continue;                   // (a launch shape, not a hint kind)
@@ -2776,7 +2656,7 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
         // the bivariate rounds' GKR corner sums (zc_biv_corner_kernel): per chip, slices of ZC_CORNER_COLS columns x blocks of 256 quads,
         // one reduction range per chip
         macro_lo[ZC_RANGE_CORNERS] = total_blocks;
-        if (biv && corner_kernel)
+        if (biv)
             for (int i = 0; i < n_chips; i++) {
                 ChipState& c = *st[i];
                 if (vrows[i] == 0) continue;
@@ -2857,8 +2737,8 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
     };
     // SP1HIP_ZC_BIVARIATE=0: the sequential first two rounds; SP1HIP_ZC_FORK=0: every launch of a round on the caller's stream
     // (A/B runs and the tests of those paths — read per call; the proof bytes are the same)
-    const bool biv_enabled = [] { const char* e = getenv("SP1HIP_ZC_BIVARIATE"); return !(e && e[0] == '0'); }();
-    const bool fork_enabled = [] { const char* e = getenv("SP1HIP_ZC_FORK"); return !(e && e[0] == '0'); }();
+    const bool biv_enabled = env_flag("SP1HIP_ZC_BIVARIATE", true);
+    const bool fork_enabled = env_flag("SP1HIP_ZC_FORK", true);
     const bool biv = biv_enabled && L >= 2;
     std::vector<std::unique_ptr<RoundPlan>> plans;           // (kept until the call returns)
     {
@@ -2897,7 +2777,6 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
                 const int n_launches = (int)rp.groups.size() + (rp.macro_n[1] ? 1 : 0) + (rp.macro_n[2] ? 1 : 0) + (rp.macro_n[3] ? 1 : 0) + (rp.macro_n[5] ? 1 : 0) + (rp.macro_n[7] ? 1 : 0);
                 const bool forked = fork_enabled && n_launches > 1 && active_provers() <= 1;
                 constexpr int N_FORK = 3;
-                const int n_fork = zc_fork_streams();
                 hipStream_t* fork_s = nullptr;
                 hipEvent_t* fork_ev = nullptr;
                 if (forked) {
@@ -2907,7 +2786,7 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
                 bool fork_used[N_FORK] = {false, false, false};
                 auto stream_of = [&](int slot) -> hipStream_t {         // slot 0: the caller's stream
                     if (!forked || slot == 0) return s;
-                    if (slot > n_fork) slot = 1 + (slot - 1) % n_fork;
+                    if (slot > ZC_N_FORK) slot = 1 + (slot - 1) % ZC_N_FORK;
                     if (!fork_used[slot - 1]) { fork_used[slot - 1] = true; (void)hipStreamWaitEvent(fork_s[slot - 1], fork_ev[0], 0); }
                     return fork_s[slot - 1];
                 };
@@ -3105,15 +2984,12 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
             // disjoint slots of d_partial: nothing orders them but the stream. They go out on fork streams — a round then
             // costs its LONGEST launch instead of their sum (five launches of 30-70 us each in the last fifteen rounds of a
             // core shard; in the large rounds one launch's tail overlaps the next one's head). SP1HIP_ZC_FORK=0: one stream.
-            static const bool fuse_nodes = [] { const char* e = getenv("SP1HIP_ZC_FUSE_NODES"); return e && e[0] == '1'; }();
             const int n_launches = (int)groups.size() + (macro_n[1] ? 1 : 0) + (macro_n[2] ? 1 : 0) + (macro_n[3] ? 1 : 0) + (macro_n[5] ? 1 : 0) + (macro_n[7] ? 1 : 0);
-            static const uint32_t fork_max_blocks = [] { const char* e = getenv("SP1HIP_ZC_FORK_MAX_BLOCKS"); return e ? (uint32_t)strtoul(e, nullptr, 10) : ZC_FORK_MAX_BLOCKS; }();
-            const bool forked = fork_enabled && n_launches > 1 && total_blocks <= fork_max_blocks && active_provers() <= 1;
+            const bool forked = fork_enabled && n_launches > 1 && total_blocks <= ZC_FORK_MAX_BLOCKS && active_provers() <= 1;
             // the round's sums reach the host through the mailbox slot when they fit it (they do for any real machine)
             const bool direct = (size_t)n_ranges * 16 + 1 <= MAILBOX_WORDS;
             const RoundSync rs_pub = direct ? RoundSync{rsync.d_counter, (volatile uint32_t*)mb.h_slot} : RoundSync{};
             constexpr int N_FORK = 3;                  // + the caller's stream = the four hardware queues a process gets by default
-            const int n_fork = zc_fork_streams();      // SP1HIP_ZC_NFORK = 1..3 fork streams (A/B knob)
             hipStream_t* fork_s = nullptr;
             hipEvent_t* fork_ev = nullptr;
             bool fork_used[N_FORK] = {false, false, false};
@@ -3146,7 +3022,7 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
                     // profiles/r04_gap_trace_timeline.txt — and four queues still beat three: 2.0 against 2.2 ms in round 2)
                     for (Launch& ln : order) {
                         int best = 0;
-                        for (int k = 1; k <= n_fork; k++) if (load[k] < load[best]) best = k;
+                        for (int k = 1; k <= ZC_N_FORK; k++) if (load[k] < load[best]) best = k;
                         ln.slot = best;
                         load[best] += ln.est;
                     }
@@ -3165,13 +3041,11 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
                 }
                 if (ln.kind == 0) {
                     const auto& g = groups[ln.group];
-                    // SP1HIP_ZC_FUSE_NODES=1: one workgroup evaluates the three nodes of its rows (rows leave HBM once). Measured
-                    // on the core-shaped shard: 12.5 ms of round kernels against 11.0 ms unfused — the re-reads of the unfused
-                    // form already meet in the memory-side cache (FETCH_SIZE counts those hits), and fusing costs a third of
-                    // the parallelism. Off by default; kept for A/B runs.
-                    const bool fused = fuse_nodes && g.n_blocks >= 4096;
-                    if (r == 0) SP1HIP_TRY(launch_round<true>(g.max_regs, g.staged, fused, dd, n_descs, g.block_lo, g.n_blocks, g.max_instr, d_eq.u32(), eq_len, d_publics.u32(), d_partial.u32(), ls));
-                    else SP1HIP_TRY(launch_round<false>(g.max_regs, g.staged, fused, dd, n_descs, g.block_lo, g.n_blocks, g.max_instr, d_eq.u32(), eq_len, d_publics.u32(), d_partial.u32(), ls));
+                    // One workgroup evaluating the three nodes of its rows (rows leave HBM once) was measured on the core-shaped
+                    // shard: 12.5 ms of round kernels against 11.0 ms with a workgroup per node — the re-reads already meet in the
+                    // memory-side cache (FETCH_SIZE counts those hits), and fusing costs a third of the parallelism. Removed.
+                    if (r == 0) SP1HIP_TRY(launch_round<true>(g.max_regs, g.staged, dd, n_descs, g.block_lo, g.n_blocks, g.max_instr, d_eq.u32(), eq_len, d_publics.u32(), d_partial.u32(), ls));
+                    else SP1HIP_TRY(launch_round<false>(g.max_regs, g.staged, dd, n_descs, g.block_lo, g.n_blocks, g.max_instr, d_eq.u32(), eq_len, d_publics.u32(), d_partial.u32(), ls));
                     continue;
                 }
 #define SP1HIP_ZC_MACRO_LAUNCH(KIND)                                                                                                   \
@@ -3191,9 +3065,7 @@ static int zerocheck_prove_impl(const sp1hip_zc_chip_t* chips, int n_chips, int 
                     SP1HIP_LAUNCH_CHECK();
                 }
                 if (ln.kind == (int)ZC_HINT_KECCAK) {
-                    const bool keccak3 = [] { const char* e = getenv("SP1HIP_ZC_KECCAK3"); return e && e[0] == '1'; }();   // (read per call: tests run both)
                     if (r == 0) hipLaunchKernelGGL((zc_macro_kernel<true, 5u>), dim3(macro_n[5] * 3), dim3(256), 0, ls, dd, n_descs, d_eq.u32(), eq_len, d_partial.u32(), macro_lo[5], dctx->d_rc);
-                    else if (keccak3) hipLaunchKernelGGL(zc_keccak3_kernel, dim3(macro_n[5]), dim3(256), 0, ls, dd, n_descs, d_eq.u32(), eq_len, d_partial.u32(), macro_lo[5]);
                     else hipLaunchKernelGGL((zc_macro_kernel<false, 5u>), dim3(macro_n[5] * 3), dim3(256), 0, ls, dd, n_descs, d_eq.u32(), eq_len, d_partial.u32(), macro_lo[5], dctx->d_rc);
                     SP1HIP_LAUNCH_CHECK();
                 }

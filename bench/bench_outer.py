@@ -10,6 +10,13 @@ the timed run issued.
 
   python bench/bench_outer.py [--repeat R] [--no-pmc] [--pmc-dir DIR]
   python bench/bench_outer.py --one NAME        (one run of one workload: what the counter runs execute)
+  python bench/bench_outer.py --basefold        (the outer BaseFold opening: profiles/outer_basefold_bench.json)
+
+--basefold times sp1hip_outer_basefold_prove at 2^16 and 2^20 rows, blowup 8, width 32, 94 queries, 22 proof-of-work bits
+(median of --repeat), splits one run by the library's ScopedTimers (batch + encode, commit phase, grinds, openings: event time
+on the stream, the commit phase includes its per-round host hand-overs), compares that commit phase with the same rounds done
+as separate sp1hip_outer_merkle_commit calls plus the inner fold kernels (alternating in one process), and measures the small-tree regime: the time of an
+outer 2^k x 8 tree for k = 1..12 minus its permutations at the batched rate, per level.
 """
 import argparse
 import csv
@@ -128,13 +135,120 @@ def counters(name, pmc_dir):
     return tot
 
 
+BF_STAGES = ["outer_bf_batch_encode", "outer_bf_commit_phase", "outer_bf_grind", "outer_bf_openings", "outer_leaf_hash_pairs",
+             "outer_compress"]
+
+
+def basefold_bench(repeat):
+    import ctypes as C
+    r = Runner()
+    api, t = r.api, r.torch
+    from sp1_amd._lib import FriConfig
+    lib = api._L()
+    out = {"workload": "outer (BN254) BaseFold opening", "gpus": 1, "log_blowup": 3, "num_queries": 94, "pow_bits": 22, "width": 32}
+    cfg = FriConfig(3, 94, 22)
+    prover = api.OuterBasefoldProver()
+    for dim in (16, 20):
+        mles = [api.ColMajor(r._kb(32 << dim), 1 << dim, 32)]
+        commit, pd = prover.commit_mles(mles, 3)
+        ch0 = api.OuterChallenger()
+        ch0.observe_commitment(commit)
+        point = ch0.sample_point(dim)
+        claims = api.BasefoldProver().evaluate_mles(mles, point)
+
+        def run():
+            return prover.prove(point, [pd], claims, ch0.clone(), cfg)
+        run()
+        ts = []
+        for _ in range(repeat):
+            t.cuda.synchronize()
+            t0 = time.perf_counter()
+            run()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts.sort()
+        out["outer_basefold_prove_2^%d_b8_x32_ms" % dim] = round(ts[len(ts) // 2], 3)
+        out["outer_basefold_prove_2^%d_b8_x32_min_max_ms" % dim] = [round(ts[0], 3), round(ts[-1], 3)]
+        # the commit phase against what a caller could do before this prover existed: per round one sp1hip_outer_merkle_commit
+        # on a width-8 pair tensor (root and commitment read back, as the transcript needs them) plus the two inner fold
+        # kernels; fused and yardstick alternate in one process
+        lg0 = dim + 3
+        pair = [api.ColMajor(r._kb(8 << (lg0 - 1 - k)), 1 << (lg0 - 1 - k), 8) for k in range(dim)]
+        cw = [api.device_words(4 << (lg0 - k)) for k in range(dim + 1)]
+        ml = [api.device_words(4 << (dim - k)) for k in range(dim + 1)]
+        cw[0].copy_(r._kb(4 << lg0))
+        ml[0].copy_(r._kb(4 << dim))
+        beta = api._ext(point[0])
+        tcs = api.OuterMerkleTcsProver()
+
+        def yardstick():
+            for k in range(dim):
+                tcs.commit_tensors([pair[k]])
+                api.check(lib.sp1hip_fold_even_odd(api._dptr(cw[k]), lg0 - k, beta, api._dptr(cw[k + 1]), None))
+                api.check(lib.sp1hip_fold_mle(api._dptr(ml[k]), dim - k, beta, api._dptr(ml[k + 1]), None))
+            t.cuda.synchronize()
+
+        def read_stages():
+            stages = {}
+            for name in BF_STAGES:
+                n_, ms_ = C.c_uint64(), C.c_double()
+                api.check(lib.sp1hip_timers_read(name.encode(), C.byref(n_), C.byref(ms_)))
+                stages[name] = {"launches": n_.value, "ms": round(ms_.value, 3)}
+            return stages
+
+        yardstick()
+        fused, yard, stages = [], [], {}
+        for _ in range(max(repeat, 5)):
+            api.check(lib.sp1hip_timers_reset())
+            api.check(lib.sp1hip_timers_enable(1))
+            run()
+            stages = read_stages()
+            api.check(lib.sp1hip_timers_enable(0))
+            fused.append(stages["outer_bf_commit_phase"]["ms"])
+            t.cuda.synchronize()
+            t0 = time.perf_counter()
+            yardstick()
+            yard.append((time.perf_counter() - t0) * 1e3)
+        fused.sort()
+        yard.sort()
+        out["stages_2^%d" % dim] = stages
+        out["commit_phase_2^%d" % dim] = {"fused_ms": round(fused[len(fused) // 2], 3), "fused_min_max_ms": [round(fused[0], 3), round(fused[-1], 3)],
+                                          "yardstick_ms": round(yard[len(yard) // 2], 3), "yardstick_min_max_ms": [round(yard[0], 3), round(yard[-1], 3)]}
+        del pair, cw, ml
+        del pd, mles
+        t.cuda.empty_cache()
+    # small trees: time of a 2^k x 8 tree against its 2^(k+1) permutations at the batched rate
+    rate = (1 << 22) / r.time("permute_2^22", 3) * 1e3
+    tcs = api.OuterMerkleTcsProver()
+    small = {}
+    for k in range(1, 13):
+        cm = api.ColMajor(r._kb(8 << k), 1 << k, 8)
+        tcs.commit_tensors([cm])
+        ts = []
+        for _ in range(max(repeat, 5)):
+            t.cuda.synchronize()
+            t0 = time.perf_counter()
+            tcs.commit_tensors([cm])
+            t.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts.sort()
+        ms = ts[len(ts) // 2]
+        thr = ((2 << k) + 1) / rate * 1e3
+        small["2^%d" % k] = {"ms": round(ms, 4), "throughput_ms": round(thr, 4), "per_level_ms": round((ms - thr) / (k + 2), 4)}
+    out["permute_per_s"] = round(rate)
+    out["small_tree_x8"] = small
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--no-pmc", action="store_true")
     ap.add_argument("--pmc-dir", default=None, help="where the counter runs write (default: a temporary directory, removed after)")
     ap.add_argument("--one")
+    ap.add_argument("--basefold", action="store_true")
     args = ap.parse_args()
+    if args.basefold:
+        return basefold_bench(args.repeat)
     if args.one:
         r = Runner()
         r.setup(args.one)()

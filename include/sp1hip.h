@@ -712,8 +712,9 @@ int sp1hip_pool_try_wait(sp1hip_pool_t* pool, sp1hip_ticket_t ticket, uint8_t* h
  * lanes 0 and 1 by reduce_31 = sum canonical(v_i) 2^(31 i)), compress = permute([l, r, 0])[0], and the transcript
  * MultiField32Challenger<KB, Fr, Perm, 3, 2>. Every BN254 value that crosses this ABI is 8 little-endian u32 words in
  * Montgomery form (R = 2^256, the Rust layout of Bn254Fr); KoalaBear words are Montgomery words (R = 2^32) as everywhere.
- * PARITY: the permutation is pinned by its published test vector; the sponge, tree, commitment and challenger are pinned only by
- * agreement of two reference statements (the device code and the in-circuit verifier), not by a reference output. */
+ * PARITY: the permutation is pinned by its published test vectors; the sponge, packing, compress, commitment cap, challenger and
+ * the 40-byte digest encoding by the reference's one real outer proof (crates/prover/wrapped_proof.bin), whose Merkle openings
+ * and whole transcript replay under tests/outer_model.py (tests/golden/make_outer_golden.py, tests/test_outer_golden.py). */
 /* d_states [n][3][8] permuted in place (device); h_states the same on the host. */
 int sp1hip_outer_poseidon2_permute(uint32_t* d_states, size_t n, sp1hip_stream_t stream);
 int sp1hip_outer_poseidon2_permute_host(uint32_t* h_states, size_t n);
@@ -746,6 +747,25 @@ int sp1hip_outer_challenger_sample_bits(sp1hip_outer_challenger_t* ch, int bits,
 int sp1hip_outer_challenger_check_witness(sp1hip_outer_challenger_t* ch, int bits, uint32_t witness, int* ok);
 int sp1hip_outer_challenger_grind(sp1hip_outer_challenger_t* ch, int bits, uint32_t* witness, sp1hip_stream_t stream);
 int sp1hip_outer_challenger_state(const sp1hip_outer_challenger_t* ch, uint32_t* out50);
+
+/* ---------------------------------------------------------------- outer (BN254) BaseFold opening
+ * The outer counterpart of sp1hip_commit_mles / sp1hip_basefold_prove: `BasefoldProver` under SP1OuterGlobalContext. The field
+ * work (batching, RS encode, folds, query gathers) is the inner prover's; trees are Poseidon2-BN254, the transcript the
+ * MultiField32Challenger (digests enter it through observe_commitment). commit_mles_data owns the codewords and the tree;
+ * h_commit receives the 8 Montgomery words of the commitment. The proof is bincode(BasefoldProof<SP1OuterGlobalContext>): the
+ * inner layout with every digest (fri_commitments, merkle_root, path entries) as u64(32) followed by the 32 little-endian
+ * bytes of the CANONICAL BN254 value (40 bytes; the serde form of Hash<KoalaBear, Bn254Fr, 1>). Size protocol and
+ * commit-on-success rule as sp1hip_basefold_prove: a NULL or too-small buffer sets *proof_len, returns
+ * SP1HIP_ERROR_BUFFER_TOO_SMALL and leaves the challenger untouched. Malformed input (a round of another dimension or blowup, a
+ * claims count other than the total width, dim + log_blowup > 24) is SP1HIP_ERROR_INVALID_ARGUMENT before any device work. */
+typedef struct sp1hip_outer_basefold_data_s sp1hip_outer_basefold_data_t;
+int sp1hip_outer_commit_mles_data(const sp1hip_tensor_t* mles, int n_mles, int lg_n, int lg_blowup, uint32_t h_commit[8],
+                                  sp1hip_outer_basefold_data_t** out, sp1hip_stream_t stream);
+void sp1hip_outer_basefold_data_free(sp1hip_outer_basefold_data_t* data);
+size_t sp1hip_outer_basefold_proof_size(int dim, const uint32_t* round_widths, int n_rounds, sp1hip_fri_config_t config);
+int sp1hip_outer_basefold_prove(const sp1hip_ext_t* h_point, int dim, sp1hip_outer_basefold_data_t* const* rounds, int n_rounds,
+                                const sp1hip_ext_t* h_claims, size_t n_claims, sp1hip_fri_config_t config,
+                                sp1hip_outer_challenger_t* challenger, uint8_t* h_proof, size_t* proof_len, sp1hip_stream_t stream);
 
 #ifdef __cplusplus
 }

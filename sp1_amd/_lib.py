@@ -172,6 +172,11 @@ PROTOTYPES = [
     ("sp1hip_outer_challenger_check_witness", None, [_vp, _int, C.c_uint32, C.POINTER(_int)]),
     ("sp1hip_outer_challenger_grind", None, [_vp, _int, u32p, _vp]),
     ("sp1hip_outer_challenger_state", None, [_vp, u32p]),
+    ("sp1hip_outer_commit_mles_data", None, [C.POINTER(Tensor), _int, _int, _int, u32p, C.POINTER(_vp), _vp]),
+    ("sp1hip_outer_basefold_data_free", "void", [_vp]),
+    ("sp1hip_outer_basefold_proof_size", _sz, [_int, u32p, _int, FriConfig]),
+    ("sp1hip_outer_basefold_prove", None, [C.POINTER(Ext), _int, C.POINTER(_vp), _int, C.POINTER(Ext), _sz, FriConfig, _vp,
+                                           u8p, C.POINTER(_sz), _vp]),
     ("sp1hip_poseidon2_permute_integer_form", None, [_vp, _sz, _vp]),
     ("sp1hip_poseidon2_permute_host", None, [_vp, _sz, _int]),
     ("sp1hip_host_permutation_is_vectorised", None, []),

@@ -897,6 +897,53 @@ def outer_commit_mles(mles, log_blowup=2, stream=None):
     return commit, cws, TcsProverData(tree, None, commit, lg_n + log_blowup, sum(m.width for m in mles))
 
 
+class OuterBasefoldProverData:
+    """Owns the codewords and the outer tree of one commitment round (sp1hip_outer_basefold_data_t)."""
+
+    def __init__(self, handle, mles, commit):
+        self.h, self.mles, self.commit = handle, mles, commit
+
+    def __del__(self):
+        if getattr(self, "h", None) and _L is not None:
+            try:
+                _L().sp1hip_outer_basefold_data_free(self.h)
+            except TypeError:                    # interpreter shutdown: the module globals are already gone
+                pass
+            self.h = None
+
+
+class OuterBasefoldProver:
+    """BasefoldProver under the outer (BN254) configuration: Poseidon2-BN254 trees, the OuterChallenger transcript, proof bytes
+    = bincode(BasefoldProof<SP1OuterGlobalContext>) with 40-byte digests (include/sp1hip.h)."""
+
+    def commit_mles(self, mles, log_blowup, stream=None):
+        """Returns (commitment: 8 Montgomery words, OuterBasefoldProverData)."""
+        lg_n = mles[0].height.bit_length() - 1
+        assert all(m.height == 1 << lg_n for m in mles)
+        commit = np.zeros(8, np.uint32)
+        handle = C.c_void_p()
+        check(_L().sp1hip_outer_commit_mles_data(_tensor_array(mles), len(mles), lg_n, log_blowup,
+                                                 commit.ctypes.data_as(_lib.u32p), C.byref(handle), _stream_ptr(stream)))
+        return commit, OuterBasefoldProverData(handle, list(mles), commit)
+
+    def proof_size(self, dim, rounds, config):
+        widths = (C.c_uint32 * len(rounds))(*[sum(m.width for m in pd.mles) for pd in rounds])
+        return _L().sp1hip_outer_basefold_proof_size(dim, widths, len(rounds), config)
+
+    def prove(self, point, rounds, claims, challenger, config, stream=None):
+        """point [dim][4], rounds: OuterBasefoldProverData per commitment round, claims [total width][4] (Montgomery words),
+        challenger: OuterChallenger, config: FriConfig. Returns the proof bytes; the challenger advances only on success."""
+        point = np.asarray(point, dtype=np.uint32).reshape(-1, 4)
+        claims = np.asarray(claims, dtype=np.uint32).reshape(-1, 4)
+        size = self.proof_size(point.shape[0], rounds, config)
+        buf = (C.c_uint8 * size)()
+        n = C.c_size_t(size)
+        handles = (C.c_void_p * len(rounds))(*[pd.h for pd in rounds])
+        check(_L().sp1hip_outer_basefold_prove(_ext_array(point), point.shape[0], handles, len(rounds), _ext_array(claims),
+                                               claims.shape[0], config, challenger.h, buf, C.byref(n), _stream_ptr(stream)))
+        return C.string_at(buf, n.value)
+
+
 class OuterChallenger:
     """MultiField32Challenger<KoalaBear, Bn254Fr, Poseidon2Bn254, 3, 2> (host transcript, device grind). Observes and samples
     KoalaBear Montgomery words like DuplexChallenger; observe_commitment takes an 8-word BN254 digest."""

@@ -23,7 +23,7 @@
 
 #include "common.hpp"
 #include "kb31.hpp"
-#include "outer_poseidon2.hpp"
+#include "outer_tree.hpp"
 #include "tensor_table.hpp"
 
 sp1hip::OuterChallenger* outer_challenger_inner(sp1hip_outer_challenger_t* ch);
@@ -33,21 +33,6 @@ namespace {
 
 using bn254::Fr;
 using bn254::MulForm;
-
-__constant__ outer::RoundConstants c_outer_rc = OUTER_RC_INIT;
-
-constexpr uint32_t OUTER_TOP_MAX = 512;       // leaves handed to the one-workgroup tail
-
-__device__ __forceinline__ Fr load_fr(const uint32_t* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    return Fr{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
-}
-__device__ __forceinline__ void store_fr(uint32_t* p, const Fr& x) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(x.w[0], x.w[1], x.w[2], x.w[3]);
-    q[1] = make_uint4(x.w[4], x.w[5], x.w[6], x.w[7]);
-}
 
 template <MulForm F>
 __global__ __launch_bounds__(256) void outer_permute_kernel(uint32_t* __restrict__ states, size_t n) {
@@ -82,12 +67,6 @@ __global__ __launch_bounds__(256) void outer_leaf_hash_kernel(const uint32_t* co
     store_fr(leaves + (size_t)row * 8, x[0]);
 }
 
-__device__ __forceinline__ Fr compress(const Fr& l, const Fr& r) {
-    Fr x[3] = {l, r, bn254::zero()};
-    outer::permute(x, c_outer_rc);
-    return x[0];
-}
-
 __global__ __launch_bounds__(256) void outer_compress_layer_kernel(const uint32_t* __restrict__ children, uint32_t n_parents,
                                                                    uint32_t* __restrict__ parents) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -98,8 +77,12 @@ __global__ __launch_bounds__(256) void outer_compress_layer_kernel(const uint32_
 // One workgroup: `layer` holds n (power of two, <= OUTER_TOP_MAX) digests, the parents follow level after level. The shape
 // digest hash([lg_height, width]) (one permutation of reduce_31([lg_height, width]) in lane 0) is computed by the last wave
 // next to the first level; then thread 0 writes the root and the commitment.
+// Optional hand-over to the host in the same launch (a BaseFold round of outer_basefold.hip waits for [4 extra words | root |
+// commitment]): payload, then — once the stores are acknowledged — the sequence number, like merkle.hip's compress_top_kernel.
 __global__ __launch_bounds__(256) void outer_compress_top_kernel(uint32_t* layer, uint32_t n, uint32_t lg_height, uint32_t total_width,
-                                                                 uint32_t* __restrict__ root_and_commit) {
+                                                                 uint32_t* __restrict__ root_and_commit,
+                                                                 const uint32_t* __restrict__ publish_extra,
+                                                                 volatile uint32_t* publish_slot, uint32_t publish_seq) {
     __shared__ uint32_t shape[8];
     if (threadIdx.x == 255) {
         uint32_t v[8] = {lg_height, total_width, 0, 0, 0, 0, 0, 0};
@@ -124,8 +107,19 @@ __global__ __launch_bounds__(256) void outer_compress_top_kernel(uint32_t* layer
     Fr s;
 #pragma unroll
     for (int k = 0; k < 8; k++) s.w[k] = shape[k];
+    const Fr commit = compress(root, s);
     store_fr(root_and_commit, root);
-    store_fr(root_and_commit + 8, compress(root, s));
+    store_fr(root_and_commit + 8, commit);
+    if (publish_slot == nullptr) return;
+#pragma unroll
+    for (int k = 0; k < 4; k++) publish_slot[1 + k] = publish_extra[k];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        publish_slot[5 + k] = root.w[k];
+        publish_slot[13 + k] = commit.w[k];
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the slot is uncached host memory: acknowledged stores, then seq
+    __hip_atomic_store(const_cast<uint32_t*>(publish_slot), publish_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // x mod p_KB for a 64-bit x = hi 2^32 + lo: hi 2^32 = mul(hi, R2) in Montgomery arithmetic (R2 = 2^64 mod p)
@@ -188,9 +182,16 @@ int merkle_commit(const sp1hip_tensor_t* tensors, int n_tensors, int lg_height, 
                            height, d_tree);
     }
     SP1HIP_LAUNCH_CHECK();
+    return outer_finish_tree(d_tree, lg_height, tw, d_root_and_commit, s);
+}
+
+}  // namespace
+
+int outer_finish_tree(uint32_t* d_tree, int lg_height, uint32_t total_width, uint32_t* d_root_and_commit, hipStream_t s,
+                      const uint32_t* d_publish_extra, uint32_t* h_publish_slot, uint32_t publish_seq) {
     ScopedTimer t("outer_compress", s);
     uint32_t* cur = d_tree;
-    uint32_t n = height;
+    uint32_t n = 1u << lg_height;
     while (n > OUTER_TOP_MAX) {
         const uint32_t np = n / 2;
         hipLaunchKernelGGL(outer_compress_layer_kernel, dim3((np + 255) / 256), dim3(256), 0, s, cur, np, cur + (size_t)n * 8);
@@ -198,12 +199,11 @@ int merkle_commit(const sp1hip_tensor_t* tensors, int n_tensors, int lg_height, 
         cur += (size_t)n * 8;
         n = np;
     }
-    hipLaunchKernelGGL(outer_compress_top_kernel, dim3(1), dim3(256), 0, s, cur, n, (uint32_t)lg_height, tw, d_root_and_commit);
+    hipLaunchKernelGGL(outer_compress_top_kernel, dim3(1), dim3(256), 0, s, cur, n, (uint32_t)lg_height, total_width,
+                       d_root_and_commit, d_publish_extra, (volatile uint32_t*)h_publish_slot, publish_seq);
     SP1HIP_LAUNCH_CHECK();
     return SP1HIP_SUCCESS;
 }
-
-}  // namespace
 }  // namespace sp1hip
 
 using namespace sp1hip;

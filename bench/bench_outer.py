@@ -11,12 +11,20 @@ the timed run issued.
   python bench/bench_outer.py [--repeat R] [--no-pmc] [--pmc-dir DIR]
   python bench/bench_outer.py --one NAME        (one run of one workload: what the counter runs execute)
   python bench/bench_outer.py --basefold        (the outer BaseFold opening: profiles/outer_basefold_bench.json)
+  python bench/bench_outer.py --jagged          (the outer stacked + jagged PCS: profiles/outer_jagged_bench.json)
 
 --basefold times sp1hip_outer_basefold_prove at 2^16 and 2^20 rows, blowup 8, width 32, 94 queries, 22 proof-of-work bits
 (median of --repeat), splits one run by the library's ScopedTimers (batch + encode, commit phase, grinds, openings: event time
 on the stream, the commit phase includes its per-round host hand-overs), compares that commit phase with the same rounds done
 as separate sp1hip_outer_merkle_commit calls plus the inner fold kernels (alternating in one process), and measures the small-tree regime: the time of an
 outer 2^k x 8 tree for k = 1..12 minus its permutations at the batched rate, per level.
+
+--jagged runs sp1hip_outer_jagged_commit of both rounds and sp1hip_outer_jagged_prove at the real wrap proof's shape (the
+(rows, cols) of tests/golden/outer_wrap_jagged.npz, seeded random tables, max_log_row_count = log_stacking_height = 21, blowup 8,
+94 queries, 22 bits): medians of --repeat with min / max (host clock around a device synchronise), one run split by the
+library's ScopedTimers, and, alternating in the same process on the same tables, what a caller had before these entry points:
+sp1hip_outer_commit_mles_data on the stacked columns (commit), and sp1hip_jagged_prove under the inner configuration minus
+its own sp1hip_basefold_prove plus sp1hip_outer_basefold_prove on the same stacked columns (prove).
 """
 import argparse
 import csv
@@ -239,6 +247,118 @@ def basefold_bench(repeat):
     print(json.dumps(out))
 
 
+JG_STAGES = ["ntt_pass0", "ntt_pass1", "ntt_pass2", "outer_leaf_hash", "outer_compress", "jagged_round0_sum", "jagged_fold0_sum", "jagged_fold_sum", "jagged_batch_evals",
+             "outer_bf_batch_encode", "outer_bf_commit_phase", "outer_bf_grind", "outer_bf_openings"]
+
+
+def jagged_bench(repeat):
+    import ctypes as C
+    import numpy as np
+    r = Runner()
+    api, t = r.api, r.torch
+    from sp1_amd._lib import FriConfig
+    lib = api._L()
+    fx = np.load(os.path.join(ROOT, "tests", "golden", "outer_wrap_jagged.npz"))
+    L = lsh = 21
+    lb, nq, pw, batch = 3, 94, 22, 64
+    cfg = FriConfig(lb, nq, pw)
+    shapes = [[(int(a), int(c)) for a, c in fx["counts%d" % k]][:-2] for k in range(2)]
+    tabs = [[api.ColMajor(r._kb(h * w), h, w) for h, w in sh] for sh in shapes]
+    ojp, ijp = api.OuterJaggedProver(L, lsh, batch, lb), api.JaggedProver(L, lsh, batch, lb)
+    obf, ibf = api.OuterBasefoldProver(), api.BasefoldProver(lb, nq, pw)
+
+    def timed(f):
+        t.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = f()
+        t.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, res
+
+    def stat(ts):
+        ts = sorted(ts)
+        return {"ms": round(ts[len(ts) // 2], 3), "min_max_ms": [round(ts[0], 3), round(ts[-1], 3)]}
+
+    def read_stages():
+        stages = {}
+        for name in JG_STAGES:
+            n_, ms_ = C.c_uint64(), C.c_double()
+            api.check(lib.sp1hip_timers_read(name.encode(), C.byref(n_), C.byref(ms_)))
+            stages[name] = {"launches": n_.value, "ms": round(ms_.value, 3)}
+        return stages
+
+    out = {"workload": "outer (BN254) stacked + jagged PCS at the wrap proof's shape", "gpus": 1, "log_blowup": lb, "num_queries": nq,
+           "pow_bits": pw, "max_log_row_count": L, "log_stacking_height": lsh, "repeat": repeat,
+           "stacked_widths": [], "areas": [sum(h * w for h, w in sh) for sh in shapes]}
+    new_c, yard_c = [[], []], [[], []]
+    commit_stages = None
+    for it in range(repeat + 1):                           # the first pass is the warm-up
+        o_rounds = []
+        for k in range(2):
+            if it == repeat:
+                api.check(lib.sp1hip_timers_reset())
+                api.check(lib.sp1hip_timers_enable(1))
+            ms, (c, sd) = timed(lambda: ojp.commit_multilinears(tabs[k]))
+            if it == repeat:
+                commit_stages = (commit_stages or []) + [read_stages()]
+                api.check(lib.sp1hip_timers_enable(0))
+            o_rounds.append((c, sd))
+            ms_y, pd = timed(lambda: obf.commit_mles(sd.batches, lb))
+            del pd
+            if it:
+                new_c[k].append(ms)
+                yard_c[k].append(ms_y)
+        if it < repeat:
+            del o_rounds
+    out["stacked_widths"] = [sum(b.width for b in sd.batches) for _, sd in o_rounds]
+    for k in range(2):
+        out["outer_jagged_commit_round%d" % k] = stat(new_c[k])
+        out["yardstick_outer_commit_mles_data_round%d" % k] = stat(yard_c[k])
+        out["commit_stages_round%d" % k] = commit_stages[k]
+    i_rounds = [ijp.commit_multilinears(tb) for tb in tabs]
+    ch_o, ch_i = api.OuterChallenger(), api.DuplexChallenger()
+    for c, _ in o_rounds:
+        ch_o.observe_commitment(c)
+    for c, _ in i_rounds:
+        ch_i.observe(c)
+    z_row = ch_o.sample_point(L)
+    claims = []
+    for tb in tabs:
+        cl = []
+        for tt in tb:
+            w = t.zeros((tt.width, 1 << L), dtype=t.int32, device="cuda")
+            w[:, :tt.height] = tt.words.view(tt.width, tt.height)
+            cl.append(np.asarray(ibf.evaluate_mles([api.ColMajor(w.view(-1), 1 << L, tt.width)], z_row)).reshape(-1, 4))
+            del w
+        claims.append(np.concatenate(cl))
+    pt = ch_o.clone().sample_point(lsh)
+    bf_claims = np.concatenate([np.asarray(ibf.evaluate_mles(sd.batches, pt)).reshape(-1, 4) for _, sd in o_rounds])
+    o_pds = [obf.commit_mles(sd.batches, lb)[1] for _, sd in o_rounds]
+    runs = {
+        "outer_jagged_prove": lambda: ojp.prove_trusted_evaluations(z_row, claims, [sd for _, sd in o_rounds], ch_o.clone(), nq, pw),
+        "inner_jagged_prove": lambda: ijp.prove_trusted_evaluations(z_row, claims, [sd for _, sd in i_rounds], ch_i.clone(), nq, pw),
+        "inner_basefold_prove": lambda: ibf.prove_trusted_mle_evaluations(pt, [sd.basefold for _, sd in i_rounds], bf_claims, ch_i.clone()),
+        "outer_basefold_prove": lambda: obf.prove(pt, o_pds, bf_claims, ch_o.clone(), cfg),
+    }
+    ts = {k: [] for k in runs}
+    yard = []
+    for it in range(repeat + 1):
+        one = {k: timed(f)[0] for k, f in runs.items()}     # alternating, one of each per pass
+        if it:
+            for k in runs:
+                ts[k].append(one[k])
+            yard.append(one["inner_jagged_prove"] - one["inner_basefold_prove"] + one["outer_basefold_prove"])
+    for k in runs:
+        out[k] = stat(ts[k])
+    out["yardstick_prove (inner jagged - inner basefold + outer basefold)"] = stat(yard)
+    api.check(lib.sp1hip_timers_reset())
+    api.check(lib.sp1hip_timers_enable(1))
+    blob = runs["outer_jagged_prove"]()
+    out["prove_stages"] = read_stages()
+    api.check(lib.sp1hip_timers_enable(0))
+    out["proof_bytes"] = len(blob)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeat", type=int, default=5)
@@ -246,9 +366,12 @@ def main():
     ap.add_argument("--pmc-dir", default=None, help="where the counter runs write (default: a temporary directory, removed after)")
     ap.add_argument("--one")
     ap.add_argument("--basefold", action="store_true")
+    ap.add_argument("--jagged", action="store_true")
     args = ap.parse_args()
     if args.basefold:
         return basefold_bench(args.repeat)
+    if args.jagged:
+        return jagged_bench(args.repeat)
     if args.one:
         r = Runner()
         r.setup(args.one)()

@@ -767,6 +767,42 @@ int sp1hip_outer_basefold_prove(const sp1hip_ext_t* h_point, int dim, sp1hip_out
                                 const sp1hip_ext_t* h_claims, size_t n_claims, sp1hip_fri_config_t config,
                                 sp1hip_outer_challenger_t* challenger, uint8_t* h_proof, size_t* proof_len, sp1hip_stream_t stream);
 
+/* ---------------------------------------------------------------- outer (BN254) stacked + jagged PCS
+ * The outer counterparts of sp1hip_stacked_commit / sp1hip_jagged_commit / sp1hip_jagged_prove, argument for argument: what a
+ * wrap-shard prover calls for `commit_traces`, the verifying key's `preprocessed_commit` and the shard proof's
+ * `evaluation_proof`. The dense stacking and the whole evaluation-proof round loop are the inner prover's; the stacked batches
+ * are committed with sp1hip_outer_commit_mles_data, the transcript is the MultiField32Challenger and the proof ends in
+ * sp1hip_outer_basefold_prove.
+ * jagged commitment = compress(stacked commitment, hash([n + 2, rows.., cols..])) under the outer sponge (the counts as
+ * KoalaBear elements, reduce_31 chunks of 8, 16 per permutation) — the rule that reproduces `main_commitment` and the vk's
+ * `preprocessed_commit` of the reference's real wrap proof (tests/test_outer_jagged_model.py).
+ * A commitment without any table value is refused (the outer tree has no zero-width leaf).
+ * The proof is bincode(JaggedPcsProof<SP1OuterGlobalContext>) in the reference's field order: the BaseFold proof
+ * (sp1hip_outer_basefold_prove's bytes), batch evaluations, the jagged and the jagged-eval sumcheck, row / column counts,
+ * `merkle_tree_commitments` (the STACKED commitments, one 40-byte digest per round), `expected_eval`, `max_log_row_count`,
+ * `log_m`. Size protocol, commit-on-success rule and argument checks as sp1hip_jagged_prove. */
+typedef struct sp1hip_outer_stacked_data_s sp1hip_outer_stacked_data_t;
+int sp1hip_outer_stacked_commit(const sp1hip_table_t* tables, int n_tables, int log_stacking_height, int batch_size, int lg_blowup,
+                                uint32_t h_commit[8], uint64_t* num_added_vals, sp1hip_outer_stacked_data_t** out,
+                                sp1hip_stream_t stream);
+int sp1hip_outer_jagged_commit(const sp1hip_table_t* tables, int n_tables, int max_log_row_count, int log_stacking_height,
+                               int batch_size, int lg_blowup, uint32_t h_commit[8], sp1hip_outer_stacked_data_t** out,
+                               sp1hip_stream_t stream);
+void sp1hip_outer_stacked_data_free(sp1hip_outer_stacked_data_t* data);
+/* Every output may be NULL. jagged_commit needs a handle from sp1hip_outer_jagged_commit; row_counts / column_counts receive
+ * *n_tables entries each (the two padding tables included) and need counts_capacity >= that. */
+int sp1hip_outer_stacked_data_info(const sp1hip_outer_stacked_data_t* data, sp1hip_outer_basefold_data_t** basefold, int* n_batches,
+                                   const uint32_t** d_dense, uint64_t* padded_area, uint32_t stacked_commit[8],
+                                   uint32_t jagged_commit[8], size_t* n_tables, uint64_t* row_counts, uint64_t* column_counts,
+                                   size_t counts_capacity);
+int sp1hip_outer_stacked_batch(const sp1hip_outer_stacked_data_t* data, int k, sp1hip_tensor_t* batch);
+/* 0 for rounds that are not jagged commitments. */
+size_t sp1hip_outer_jagged_proof_size(sp1hip_outer_stacked_data_t* const* rounds, int n_rounds, sp1hip_fri_config_t config);
+int sp1hip_outer_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1hip_outer_stacked_data_t* const* rounds,
+                              int n_rounds, const sp1hip_ext_t* h_claims, const size_t* claims_per_round,
+                              sp1hip_fri_config_t config, sp1hip_outer_challenger_t* challenger, uint8_t* h_proof,
+                              size_t* proof_len, sp1hip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

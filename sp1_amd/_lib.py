@@ -177,6 +177,16 @@ PROTOTYPES = [
     ("sp1hip_outer_basefold_proof_size", _sz, [_int, u32p, _int, FriConfig]),
     ("sp1hip_outer_basefold_prove", None, [C.POINTER(Ext), _int, C.POINTER(_vp), _int, C.POINTER(Ext), _sz, FriConfig, _vp,
                                            u8p, C.POINTER(_sz), _vp]),
+    ("sp1hip_outer_stacked_commit", None, [C.POINTER(Table), _int, _int, _int, _int, u32p, C.POINTER(C.c_uint64),
+                                           C.POINTER(_vp), _vp]),
+    ("sp1hip_outer_jagged_commit", None, [C.POINTER(Table), _int, _int, _int, _int, _int, u32p, C.POINTER(_vp), _vp]),
+    ("sp1hip_outer_stacked_data_free", "void", [_vp]),
+    ("sp1hip_outer_stacked_data_info", None, [_vp, C.POINTER(_vp), C.POINTER(_int), C.POINTER(_vp), C.POINTER(C.c_uint64), u32p,
+                                              u32p, C.POINTER(_sz), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _sz]),
+    ("sp1hip_outer_stacked_batch", None, [_vp, _int, C.POINTER(Tensor)]),
+    ("sp1hip_outer_jagged_proof_size", _sz, [C.POINTER(_vp), _int, FriConfig]),
+    ("sp1hip_outer_jagged_prove", None, [C.POINTER(Ext), _int, C.POINTER(_vp), _int, C.POINTER(Ext), C.POINTER(_sz), FriConfig,
+                                         _vp, u8p, C.POINTER(_sz), _vp]),
     ("sp1hip_poseidon2_permute_integer_form", None, [_vp, _sz, _vp]),
     ("sp1hip_poseidon2_permute_host", None, [_vp, _sz, _int]),
     ("sp1hip_host_permutation_is_vectorised", None, []),

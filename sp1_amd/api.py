@@ -1008,3 +1008,99 @@ class OuterChallenger:
             except TypeError:                    # interpreter shutdown: the module globals are already gone
                 pass
             self.h = None
+
+
+class OuterStackedData:
+    """Owns the dense stacked buffer and the outer BaseFold data of one outer commitment (sp1hip_outer_stacked_data_t).
+    commit: the stacked commitment; jagged_commit, row_counts, column_counts (the two padding tables included): set when the
+    handle came from OuterJaggedProver."""
+
+    def __init__(self, handle, num_added_vals, log_stacking_height, jagged):
+        self.h, self.num_added_vals, self.lsh = handle, num_added_vals, log_stacking_height
+        bf, nb, dense, padded, nt = C.c_void_p(), C.c_int(), C.c_void_p(), C.c_uint64(), C.c_size_t()
+        self.commit = np.zeros(8, np.uint32)
+        check(_L().sp1hip_outer_stacked_data_info(handle, C.byref(bf), C.byref(nb), C.byref(dense), C.byref(padded),
+                                                  self.commit.ctypes.data_as(_lib.u32p), None, C.byref(nt), None, None, 0))
+        self.padded_area, self.basefold_handle = padded.value, bf
+        self.jagged_commit, self.row_counts, self.column_counts = None, [], []
+        if jagged:
+            self.jagged_commit = np.zeros(8, np.uint32)
+            rows, cols = (C.c_uint64 * nt.value)(), (C.c_uint64 * nt.value)()
+            check(_L().sp1hip_outer_stacked_data_info(handle, None, None, None, None, None,
+                                                      self.jagged_commit.ctypes.data_as(_lib.u32p), None, rows, cols, nt.value))
+            self.row_counts, self.column_counts = list(rows), list(cols)
+        self.batches = []
+        for k in range(nb.value):
+            t = Tensor()
+            check(_L().sp1hip_outer_stacked_batch(handle, k, C.byref(t)))
+            self.batches.append(_RawColMajor(t.d_data, 1 << log_stacking_height, t.width))
+
+    def __del__(self):
+        if getattr(self, "h", None) and _L is not None:
+            try:
+                _L().sp1hip_outer_stacked_data_free(self.h)
+            except TypeError:                    # interpreter shutdown: the module globals are already gone
+                pass
+            self.h = None
+
+
+class OuterStackedPcsProver:
+    """StackedPcsProver under the outer (BN254) configuration."""
+
+    def __init__(self, log_stacking_height, batch_size, log_blowup=3):
+        self.lsh, self.batch_size, self.log_blowup = log_stacking_height, batch_size, log_blowup
+
+    def commit_multilinears(self, tables, stream=None):
+        commit = np.zeros(8, np.uint32)
+        added, handle = C.c_uint64(), C.c_void_p()
+        check(_L().sp1hip_outer_stacked_commit(_table_array(tables), len(tables), self.lsh, self.batch_size, self.log_blowup,
+                                               commit.ctypes.data_as(_lib.u32p), C.byref(added), C.byref(handle),
+                                               _stream_ptr(stream)))
+        return commit, OuterStackedData(handle, added.value, self.lsh, False), added.value
+
+
+class OuterJaggedProver:
+    """JaggedProver under the outer (BN254) configuration: commit_multilinears over chip tables (zero-row tables are counted,
+    not committed) and the whole evaluation proof, on an OuterChallenger."""
+
+    def __init__(self, max_log_row_count, log_stacking_height, batch_size, log_blowup=3):
+        self.max_log_row_count, self.lsh = max_log_row_count, log_stacking_height
+        self.batch_size, self.log_blowup = batch_size, log_blowup
+
+    def commit_multilinears(self, tables, stream=None):
+        commit = np.zeros(8, np.uint32)
+        handle = C.c_void_p()
+        check(_L().sp1hip_outer_jagged_commit(_table_array(tables), len(tables), self.max_log_row_count, self.lsh,
+                                              self.batch_size, self.log_blowup, commit.ctypes.data_as(_lib.u32p),
+                                              C.byref(handle), _stream_ptr(stream)))
+        return commit, OuterStackedData(handle, None, self.lsh, True)
+
+    def _args(self, z_row, claims_per_round, rounds, challenger, num_queries, pow_bits):
+        z_row = np.ascontiguousarray(np.asarray(z_row, dtype=np.uint32).reshape(-1, 4))
+        assert z_row.shape[0] == self.max_log_row_count
+        cl = [np.asarray(c, dtype=np.uint32).reshape(-1, 4) for c in claims_per_round]
+        flat = np.ascontiguousarray(np.concatenate(cl)) if cl else np.zeros((0, 4), np.uint32)
+        counts = (C.c_size_t * len(rounds))(*[c.shape[0] for c in cl])
+        hs = (C.c_void_p * len(rounds))(*[r.h for r in rounds])
+        cfg = FriConfig(self.log_blowup, num_queries, pow_bits)
+        return [_ext_array(z_row), self.max_log_row_count, hs, len(rounds), _ext_array(flat) if flat.size else None, counts,
+                cfg, challenger.h]
+
+    def proof_size(self, rounds, num_queries, pow_bits):
+        hs = (C.c_void_p * len(rounds))(*[r.h for r in rounds])
+        return _L().sp1hip_outer_jagged_proof_size(hs, len(rounds), FriConfig(self.log_blowup, num_queries, pow_bits))
+
+    def prove_trusted_evaluations(self, z_row, claims_per_round, rounds, challenger, num_queries=94, pow_bits=22, stream=None):
+        """JaggedProver::prove_trusted_evaluations (/root/reference/slop/crates/jagged/src/prover.rs:L162-L328) under the outer
+        configuration. rounds: the OuterStackedData of every commitment round, in order; claims_per_round[r]: [n_cols_r][4]
+        column evaluations at z_row of round r's tables; challenger: an OuterChallenger, advanced on success only. Returns
+        bincode(JaggedPcsProof<SP1OuterGlobalContext>)."""
+        args = self._args(z_row, claims_per_round, rounds, challenger, num_queries, pow_bits)
+        n = C.c_size_t(0)
+        st = _L().sp1hip_outer_jagged_prove(*args, None, C.byref(n), _stream_ptr(stream))
+        if st != _lib.ERROR_BUFFER_TOO_SMALL:                                   # anything but BUFFER_TOO_SMALL is a real error
+            check(st)
+            raise RuntimeError("size query unexpectedly succeeded")
+        buf = (C.c_uint8 * n.value)()
+        check(_L().sp1hip_outer_jagged_prove(*args, buf, C.byref(n), _stream_ptr(stream)))
+        return C.string_at(buf, n.value)

@@ -35,6 +35,7 @@
 #include <array>
 
 #include "device_ctx.hpp"
+#include "jagged_host.hpp"
 #include "round_sync.hpp"
 #include "stacked_data.hpp"
 #include "tensor_table.hpp"
@@ -767,9 +768,9 @@ std::array<Ext, 3> interpolate(const Ext& y0, const Ext& h4, const Ext& y1) {
     return {y0, y1 - y0 - c2, c2};
 }
 
-Ext observe_and_sample(sp1hip_challenger_t* ch, const std::array<Ext, 3>& poly) {
-    for (auto& c : poly) for (int k = 0; k < 4; k++) challenger_observe(ch, c.c[k]);
-    return challenger_sample_ext(ch);
+Ext observe_and_sample(JaggedBackend& ch, const std::array<Ext, 3>& poly) {
+    for (auto& c : poly) for (int k = 0; k < 4; k++) ch.observe(c.c[k]);
+    return ch.sample_ext();
 }
 
 struct Scratch {                    // device scratch shared by all rounds of one proof
@@ -838,7 +839,7 @@ int upload(DeviceBuf& buf, const void* src, size_t bytes, hipStream_t s, PinnedS
 
 // JaggedEvalSumcheckProver::prove_jagged_evaluation. prefix: #columns + 1 dense prefix sums.
 int jagged_eval_prove(const std::vector<uint32_t>& prefix, int log_m, const std::vector<Ext>& z_row, const std::vector<Ext>& z_col,
-                      const std::vector<Ext>& z_trace, sp1hip_challenger_t* ch, Scratch& sc, Sumcheck* proof) {
+                      const std::vector<Ext>& z_trace, JaggedBackend& ch, Scratch& sc, Sumcheck* proof) {
     hipStream_t s = sc.s;
     const int D = log_m + 1, dim = 2 * D;
     // condensed (t_c, t_{c+1}) runs with their summed eq(z_col, .) weights (sumcheck_poly.rs:L106-L121)
@@ -868,7 +869,7 @@ int jagged_eval_prove(const std::vector<uint32_t>& prefix, int log_m, const std:
     SP1HIP_LAUNCH_CHECK();
     Ext expected_sum, unused;
     SP1HIP_TRY(sc.finish(nb, &expected_sum, &unused));
-    for (int k = 0; k < 4; k++) challenger_observe(ch, expected_sum.c[k]);
+    for (int k = 0; k < 4; k++) ch.observe(expected_sum.c[k]);
 
     proof->claimed_sum = expected_sum;
     const Ext half = kb::ext_inv(ext_c(2));
@@ -931,31 +932,32 @@ int jagged_eval_prove(const std::vector<uint32_t>& prefix, int log_m, const std:
 
 }  // namespace
 
-// bincode(JaggedPcsProof) size: BaseFold proof + batch evaluations + two sumchecks + counts + commitments + tail
-size_t jagged_proof_size(int lsh, const std::vector<uint32_t>& round_widths, const std::vector<size_t>& tables_per_round,
-                         uint64_t total_area, sp1hip_fri_config_t config) {
+size_t jagged_proof_size_with(size_t opening_bytes, size_t commitment_bytes, const std::vector<uint32_t>& round_widths,
+                              const std::vector<size_t>& tables_per_round, uint64_t total_area) {
     const int n_rounds = (int)round_widths.size();
     const int log_m = log2_ceil(total_area), D = log_m + 1;
-    size_t need = sp1hip_basefold_proof_size(lsh, round_widths.data(), n_rounds, config);
+    size_t need = opening_bytes;
     need += 8;
     for (uint32_t w : round_widths) need += 8 + (size_t)w * 16 + 16;
     need += 8 + (size_t)log_m * (8 + 48) + 16 + 8 + (size_t)log_m * 16 + 16;
     need += 8 + (size_t)2 * D * (8 + 48) + 16 + 8 + (size_t)2 * D * 16 + 16;
     need += 8;
     for (size_t t : tables_per_round) need += 8 + t * 16;
-    need += 8 + (size_t)n_rounds * 32 + 16 + 8 + 8;
+    need += 8 + (size_t)n_rounds * commitment_bytes + 16 + 8 + 8;
     return need;
 }
-}  // namespace sp1hip
 
-using namespace sp1hip;
+// the inner configuration's size (also what shard.hip sizes a shard proof with)
+size_t jagged_proof_size(int lsh, const std::vector<uint32_t>& round_widths, const std::vector<size_t>& tables_per_round,
+                         uint64_t total_area, sp1hip_fri_config_t config) {
+    return jagged_proof_size_with(sp1hip_basefold_proof_size(lsh, round_widths.data(), (int)round_widths.size(), config), 32, round_widths,
+                                  tables_per_round, total_area);
+}
 
-extern "C" {
-
-int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1hip_stacked_data_t* const* rounds, int n_rounds,
-                        const sp1hip_ext_t* h_claims, const size_t* claims_per_round, sp1hip_fri_config_t config,
-                        sp1hip_challenger_t* challenger, uint8_t* h_proof, size_t* proof_len, sp1hip_stream_t stream) {
-    SP1HIP_REQUIRE(h_z_row && rounds && n_rounds > 0 && n_rounds <= 8 && claims_per_round && challenger && proof_len, "bad argument");
+int jagged_prove_with(JaggedBackend& be, const sp1hip_ext_t* h_z_row, int max_log_row_count, StackedCore* const* rounds, int n_rounds,
+                      const sp1hip_ext_t* h_claims, const size_t* claims_per_round, sp1hip_fri_config_t config, uint8_t* h_proof,
+                      size_t* proof_len, sp1hip_stream_t stream) {
+    SP1HIP_REQUIRE(h_z_row && rounds && n_rounds > 0 && n_rounds <= 8 && claims_per_round && proof_len, "bad argument");
     SP1HIP_REQUIRE(max_log_row_count >= 0 && max_log_row_count <= 30, "max_log_row_count out of range");
     hipStream_t s = S(stream);
     // SP1HIP_JG_TIMING=1: host wall time of the call's parts on stderr
@@ -968,13 +970,14 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
         ~StageMarks() { if (open) roctx_pop(); }
     } marks;
     marks.next("jagged_setup");
+    SP1HIP_REQUIRE(rounds[0], "null round");
     const int lsh = rounds[0]->log_stacking_height;
     SP1HIP_REQUIRE(lsh >= 1, "log_stacking_height must be at least 1");
     uint64_t total_cols = 0, total_area = 0, n_claims = 0;
     std::vector<uint32_t> round_widths;
     for (int r = 0; r < n_rounds; r++) {
-        const sp1hip_stacked_data_s* d = rounds[r];
-        SP1HIP_REQUIRE(d && d->jagged, "round data did not come from sp1hip_jagged_commit");
+        const StackedCore* d = rounds[r];
+        SP1HIP_REQUIRE(d && d->jagged, "round data did not come from a jagged commit");
         if (d->stream != s) rounds[r]->foreign_use = true;
         SP1HIP_REQUIRE(d->log_stacking_height == lsh && d->max_log_row_count == max_log_row_count, "rounds disagree on parameters");
         SP1HIP_REQUIRE(d->area > 0, "a commitment round without any table data cannot be opened");
@@ -993,23 +996,23 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
     const int num_col_variables = log2_ceil(total_cols);
     std::vector<size_t> tables_per_round;
     for (int r = 0; r < n_rounds; r++) tables_per_round.push_back(rounds[r]->row_counts.size());
-    const size_t need = jagged_proof_size(lsh, round_widths, tables_per_round, total_area, config);
+    const size_t need = jagged_proof_size_with(be.opening_size(lsh, round_widths.data(), n_rounds, config), be.commitment_bytes(),
+                                               round_widths, tables_per_round, total_area);
     if (!h_proof || *proof_len < need) {
         *proof_len = need;
-        set_error("sp1hip_jagged_prove: proof buffer too small, need %zu bytes", need);
+        set_error("%s: proof buffer too small, need %zu bytes", be.entry_point(), need);
         return SP1HIP_ERROR_BUFFER_TOO_SMALL;
     }
     const DeviceCtx* ctx;
     SP1HIP_TRY(get_device_ctx(&ctx));
 
     // work on a copy of the transcript; commit it only on success
-    sp1hip_challenger_t* ch = nullptr;
-    SP1HIP_TRY(sp1hip_challenger_clone(challenger, &ch));
-    struct ChGuard { sp1hip_challenger_t* c; ~ChGuard() { sp1hip_challenger_free(c); } } guard{ch};
+    JaggedBackend& ch = be;
+    SP1HIP_TRY(be.begin());
 
     std::vector<Ext> z_row(max_log_row_count), z_col(num_col_variables);
     memcpy(z_row.data(), h_z_row, (size_t)max_log_row_count * 16);
-    for (auto& z : z_col) z = challenger_sample_ext(ch);
+    for (auto& z : z_col) z = ch.sample_ext();
 
     // column claims with the zero claims of the padding columns, padded to a power of two (prover.rs:L187-L212, L268-L271)
     std::vector<Ext> column_claims;
@@ -1119,7 +1122,7 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
             uint64_t seg_start = 0;
             uint32_t col = 0;
             for (int r = 0; r < n_rounds; r++) {
-                const sp1hip_stacked_data_s* d = rounds[r];
+                const StackedCore* d = rounds[r];
                 uint64_t off = 0;
                 const size_t n_real = d->row_counts.size() - 2;           // the two padding tables hold zeros only
                 for (size_t t = 0; t < d->row_counts.size(); t++) {
@@ -1317,13 +1320,12 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
     marks.next("stacked_basefold_open");
 
     // ---- dense PCS: observe the claim, evaluate every stacked column at the stack point, BaseFold-open
-    for (int k = 0; k < 4; k++) challenger_observe(ch, q_eval.c[k]);
+    for (int k = 0; k < 4; k++) ch.observe(q_eval.c[k]);
     const std::vector<Ext> stack_point(final_point.end() - lsh, final_point.end());
     DeviceBuf d_eq, d_evals;
     SP1HIP_TRY(d_eq.alloc(((size_t)16) << lsh, s));
     SP1HIP_TRY(sp1hip_partial_lagrange(reinterpret_cast<const sp1hip_ext_t*>(stack_point.data()), lsh, d_eq.u32(), stream));
     std::vector<std::vector<Ext>> batch_evals(n_rounds);
-    std::vector<sp1hip_basefold_data_t*> bf;
     std::vector<Ext> flat_claims;
     SP1HIP_TRY(d_evals.alloc((size_t)(*std::max_element(round_widths.begin(), round_widths.end())) * 16, s));
     for (int r = 0; r < n_rounds; r++) {
@@ -1333,15 +1335,13 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
         SP1HIP_TRY(sp1hip_mle_eval_columns(rounds[r]->batches.data(), (int)rounds[r]->batches.size(), lsh, d_eq.u32(), d_evals.u32(), stream));
         SP1HIP_TRY(sc.mb.fetch(d_evals.p, (size_t)w * 4, batch_evals[r].data()));
         flat_claims.insert(flat_claims.end(), batch_evals[r].begin(), batch_evals[r].end());
-        bf.push_back(rounds[r]->basefold);
     }
-    for (auto& e : flat_claims) for (int k = 0; k < 4; k++) challenger_observe(ch, e.c[k]);
+    for (auto& e : flat_claims) for (int k = 0; k < 4; k++) ch.observe(e.c[k]);
     jg_t[4] = std::chrono::steady_clock::now();
     // the BaseFold proof is the first field of JaggedPcsProof: it is written straight into the caller's buffer, the rest behind it
     size_t bf_len = need;
-    SP1HIP_TRY(sp1hip_basefold_prove(reinterpret_cast<const sp1hip_ext_t*>(stack_point.data()), lsh, bf.data(), n_rounds,
-                                     reinterpret_cast<const sp1hip_ext_t*>(flat_claims.data()), flat_claims.size(), config, ch,
-                                     h_proof, &bf_len, stream));
+    SP1HIP_TRY(be.open(reinterpret_cast<const sp1hip_ext_t*>(stack_point.data()), lsh,
+                       reinterpret_cast<const sp1hip_ext_t*>(flat_claims.data()), flat_claims.size(), config, h_proof, &bf_len, stream));
 
     // ---- bincode(JaggedPcsProof)
     jg_t[5] = std::chrono::steady_clock::now();
@@ -1359,7 +1359,11 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
         for (size_t t = 0; t < rounds[r]->row_counts.size(); t++) { w.u64(rounds[r]->row_counts[t]); w.u64(rounds[r]->column_counts[t]); }
     }
     w.u64(n_rounds);
-    for (int r = 0; r < n_rounds; r++) for (int k = 0; k < 8; k++) w.felt(rounds[r]->commit[k]);
+    for (int r = 0; r < n_rounds; r++) {
+        uint8_t c[64];
+        be.write_commitment(r, c);
+        w.raw(c, be.commitment_bytes());
+    }
     w.ext(q_eval);
     w.u64(max_log_row_count);
     w.u64(log_m);
@@ -1368,7 +1372,7 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
         return SP1HIP_ERROR_RUNTIME;
     }
     *proof_len = w.n;
-    challenger_restore(challenger, ch);
+    be.accept();
     if (jg_timing) {
         jg_t[6] = std::chrono::steady_clock::now();
         const auto ms = [&](int a, int b) { return std::chrono::duration<double, std::milli>(jg_t[b] - jg_t[a]).count(); };
@@ -1376,6 +1380,51 @@ int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1h
                 ms(0, 1), log_m, ms(1, 2), ms(2, 3), ms(3, 4), ms(4, 5), ms(5, 6));
     }
     return SP1HIP_SUCCESS;
+}
+
+namespace {
+// The inner configuration: the KoalaBear DuplexChallenger, sp1hip_basefold_prove, a commitment of 8 KoalaBear words.
+struct InnerJaggedBackend final : JaggedBackend {
+    sp1hip_challenger_t* caller;
+    sp1hip_challenger_t* work = nullptr;
+    sp1hip_stacked_data_t* const* rounds;
+    int n_rounds;
+    InnerJaggedBackend(sp1hip_challenger_t* c, sp1hip_stacked_data_t* const* r, int n) : caller(c), rounds(r), n_rounds(n) {}
+    ~InnerJaggedBackend() override { sp1hip_challenger_free(work); }
+    const char* entry_point() const override { return "sp1hip_jagged_prove"; }
+    int begin() override { return sp1hip_challenger_clone(caller, &work); }
+    void observe(uint32_t monty) override { challenger_observe(work, monty); }
+    Ext sample_ext() override { return challenger_sample_ext(work); }
+    void accept() override { challenger_restore(caller, work); }
+    size_t opening_size(int dim, const uint32_t* widths, int n, sp1hip_fri_config_t config) const override {
+        return sp1hip_basefold_proof_size(dim, widths, n, config);
+    }
+    int open(const sp1hip_ext_t* h_point, int dim, const sp1hip_ext_t* h_claims, size_t n_claims, sp1hip_fri_config_t config,
+             uint8_t* h_proof, size_t* len, sp1hip_stream_t stream) override {
+        std::vector<sp1hip_basefold_data_t*> bf;
+        for (int r = 0; r < n_rounds; r++) bf.push_back(rounds[r]->basefold);
+        return sp1hip_basefold_prove(h_point, dim, bf.data(), n_rounds, h_claims, n_claims, config, work, h_proof, len, stream);
+    }
+    size_t commitment_bytes() const override { return 32; }
+    void write_commitment(int round, uint8_t* dst) const override {
+        for (int k = 0; k < 8; k++) { const uint32_t v = kb::from_monty(rounds[round]->commit[k]); memcpy(dst + 4 * k, &v, 4); }
+    }
+};
+}  // namespace
+}  // namespace sp1hip
+
+using namespace sp1hip;
+
+extern "C" {
+
+int sp1hip_jagged_prove(const sp1hip_ext_t* h_z_row, int max_log_row_count, sp1hip_stacked_data_t* const* rounds, int n_rounds,
+                        const sp1hip_ext_t* h_claims, const size_t* claims_per_round, sp1hip_fri_config_t config,
+                        sp1hip_challenger_t* challenger, uint8_t* h_proof, size_t* proof_len, sp1hip_stream_t stream) {
+    SP1HIP_REQUIRE(rounds && n_rounds > 0 && n_rounds <= 8 && challenger, "bad argument");
+    std::vector<StackedCore*> cores(rounds, rounds + n_rounds);
+    InnerJaggedBackend be(challenger, rounds, n_rounds);
+    return jagged_prove_with(be, h_z_row, max_log_row_count, cores.data(), n_rounds, h_claims, claims_per_round, config, h_proof,
+                             proof_len, stream);
 }
 
 }  // extern "C"

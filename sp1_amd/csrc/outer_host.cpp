@@ -138,6 +138,29 @@ void outer_host_from_monty(const uint32_t (&in)[8], uint32_t (&out)[8]) {
     to32(mulm(from32(in), one), out);
 }
 
+void outer_host_hash(const uint32_t* canonical, size_t n, uint32_t (&out)[8]) {
+    uint32_t st[3][8] = {};
+    for (size_t c = 0; c < n; c += 16) {
+        const size_t k = n - c < 16 ? n - c : 16;
+        uint32_t packed[8];
+        pack_chunk(canonical + c, (int)(k < 8 ? k : 8), packed);
+        outer_host_to_monty(packed, st[0]);
+        if (k > 8) {
+            pack_chunk(canonical + c + 8, (int)(k - 8), packed);
+            outer_host_to_monty(packed, st[1]);
+        }
+        outer_host_permute(st);
+    }
+    memcpy(out, st[0], 32);
+}
+void outer_host_compress(const uint32_t (&l)[8], const uint32_t (&r)[8], uint32_t (&out)[8]) {
+    uint32_t st[3][8] = {};
+    memcpy(st[0], l, 32);
+    memcpy(st[1], r, 32);
+    outer_host_permute(st);
+    memcpy(out, st[0], 32);
+}
+
 void OuterChallenger::duplexing() {
     for (int c = 0; 8 * c < n_in; c++) {
         uint32_t packed[8];

@@ -85,6 +85,11 @@ void outer_host_permute(uint32_t (&state)[3][8]);
 // Host helpers on 8-word values: canonical -> Montgomery, Montgomery -> canonical.
 void outer_host_to_monty(const uint32_t (&in)[8], uint32_t (&out)[8]);
 void outer_host_from_monty(const uint32_t (&in)[8], uint32_t (&out)[8]);
+// The outer sponge and compressor on the host, for the few permutations of a commitment's metadata (the jagged wrap):
+// MultiField32PaddingFreeSponge over n canonical KoalaBear words (reduce_31 chunks of 8, 16 words per permutation, a short
+// last block leaves the lanes it does not reach as they are) and compress = permute([l, r, 0])[0]. Digests: Montgomery words.
+void outer_host_hash(const uint32_t* canonical, size_t n, uint32_t (&out)[8]);
+void outer_host_compress(const uint32_t (&l)[8], const uint32_t (&r)[8], uint32_t (&out)[8]);
 
 // MultiField32Challenger<KoalaBear, Bn254Fr, Perm, 3, 2> (stated in full by the in-circuit verifier of outer proofs,
 // /root/reference/crates/recursion/circuit/src/challenger.rs:L258-L345, L455-L473). KoalaBear words are kept canonical.

@@ -63,15 +63,13 @@ void host_compress(const uint32_t l[8], const uint32_t r[8], uint32_t out[8]) {
 }
 }  // namespace
 
-extern "C" {
+namespace sp1hip {
 
-int sp1hip_stacked_commit(const sp1hip_table_t* tables, int n_tables, int log_stacking_height, int batch_size,
-                          int lg_blowup, uint32_t h_commit[8], uint64_t* num_added_vals, sp1hip_stacked_data_t** out,
-                          sp1hip_stream_t stream) {
-    SP1HIP_REQUIRE((tables || n_tables == 0) && n_tables >= 0 && h_commit && out, "bad argument");
+int stacked_commit_dense(const sp1hip_table_t* tables, int n_tables, int log_stacking_height, int batch_size, int lg_blowup,
+                         StackedCore* sd, uint64_t* num_added_vals, hipStream_t s, const std::function<int(const FillBatch&)>& commit) {
+    SP1HIP_REQUIRE((tables || n_tables == 0) && n_tables >= 0 && sd, "bad argument");
     SP1HIP_REQUIRE(log_stacking_height >= 0 && log_stacking_height + lg_blowup <= kb::TWO_ADICITY, "stacking height out of range");
     SP1HIP_REQUIRE(batch_size >= 1, "batch_size must be positive");
-    hipStream_t s = S(stream);
     const DeviceCtx* ctx;
     SP1HIP_TRY(get_device_ctx(&ctx));
     const uint64_t H = (uint64_t)1 << log_stacking_height;
@@ -83,7 +81,6 @@ int sp1hip_stacked_commit(const sp1hip_table_t* tables, int n_tables, int log_st
     // next multiple of the stacking height, at least one column (prover.rs:L72-L79)
     uint64_t padded = ((area + H - 1) / H) * H;
     if (padded < H) padded = H;
-    std::unique_ptr<sp1hip_stacked_data_s> sd(new sp1hip_stacked_data_s());
     sd->stream = s;
     sd->area = area;
     sd->padded = padded;
@@ -133,10 +130,62 @@ int sp1hip_stacked_commit(const sp1hip_table_t* tables, int n_tables, int log_st
         sd->batches.push_back({(const uint32_t*)sd->d_dense + c0 * H, w});
     }
     SP1HIP_REQUIRE(sd->batches.size() <= 128, "more than 128 stacked batches in one commitment");
-    SP1HIP_TRY(commit_mles_hooked(sd->batches.data(), (int)sd->batches.size(), log_stacking_height, lg_blowup, sd->commit,
-                                  &sd->basefold, stream, &fill_batch));
-    memcpy(h_commit, sd->commit, 32);
+    SP1HIP_TRY(commit(fill_batch));
     if (num_added_vals) *num_added_vals = padded - area;
+    return SP1HIP_SUCCESS;
+}
+
+int jagged_select_tables(const sp1hip_table_t* tables, int n_tables, int max_log_row_count, JaggedTables* out) {
+    SP1HIP_REQUIRE((tables || n_tables == 0) && out, "bad argument");
+    SP1HIP_REQUIRE(max_log_row_count >= 0 && max_log_row_count <= 30, "max_log_row_count out of range");
+    const uint64_t M = (uint64_t)1 << max_log_row_count;
+    // only tables with real rows go to the dense PCS (prover.rs:L129-L131); all of them are counted
+    for (int i = 0; i < n_tables; i++) {
+        SP1HIP_REQUIRE(tables[i].rows <= M, "table taller than 2^max_log_row_count");
+        out->rows.push_back(tables[i].rows);
+        out->cols.push_back(tables[i].cols);
+        if (tables[i].rows) out->dense.push_back(tables[i]);
+    }
+    return SP1HIP_SUCCESS;
+}
+
+std::vector<uint32_t> jagged_finish_counts(uint64_t added, int max_log_row_count, JaggedTables&& t, StackedCore* sd) {
+    const uint64_t M = (uint64_t)1 << max_log_row_count;
+    // two dummy tables account for the stacking padding (prover.rs:L133-L139)
+    uint64_t added_cols = (added + M - 1) / M;
+    if (added_cols < 1) added_cols = 1;
+    t.rows.push_back(M);
+    t.rows.push_back(added - (added_cols - 1) * M);
+    t.cols.push_back(added_cols - 1);
+    t.cols.push_back(1);
+    std::vector<uint32_t> meta;
+    meta.push_back((uint32_t)t.rows.size());
+    for (uint64_t r : t.rows) meta.push_back((uint32_t)r);
+    for (uint64_t c : t.cols) meta.push_back((uint32_t)c);
+    // what the evaluation proof (jagged.hip) needs later: JaggedProverData (prover.rs:L150-L156)
+    sd->jagged = true;
+    sd->max_log_row_count = max_log_row_count;
+    sd->row_counts = std::move(t.rows);
+    sd->column_counts = std::move(t.cols);
+    sd->padding_column_count = added_cols;
+    return meta;
+}
+
+}  // namespace sp1hip
+
+extern "C" {
+
+int sp1hip_stacked_commit(const sp1hip_table_t* tables, int n_tables, int log_stacking_height, int batch_size,
+                          int lg_blowup, uint32_t h_commit[8], uint64_t* num_added_vals, sp1hip_stacked_data_t** out,
+                          sp1hip_stream_t stream) {
+    SP1HIP_REQUIRE(h_commit && out, "bad argument");
+    std::unique_ptr<sp1hip_stacked_data_s> sd(new sp1hip_stacked_data_s());
+    SP1HIP_TRY(stacked_commit_dense(tables, n_tables, log_stacking_height, batch_size, lg_blowup, sd.get(), num_added_vals, S(stream),
+                                    [&](const FillBatch& fill_batch) {
+        return commit_mles_hooked(sd->batches.data(), (int)sd->batches.size(), log_stacking_height, lg_blowup, sd->commit,
+                                  &sd->basefold, stream, &fill_batch);
+    }));
+    memcpy(h_commit, sd->commit, 32);
     *out = sd.release();
     return SP1HIP_SUCCESS;
 }
@@ -162,42 +211,18 @@ int sp1hip_stacked_batch(const sp1hip_stacked_data_t* data, int k, sp1hip_tensor
 int sp1hip_jagged_commit(const sp1hip_table_t* tables, int n_tables, int max_log_row_count, int log_stacking_height,
                          int batch_size, int lg_blowup, uint32_t h_commit[8], sp1hip_stacked_data_t** out,
                          sp1hip_stream_t stream) {
-    SP1HIP_REQUIRE((tables || n_tables == 0) && h_commit && out, "bad argument");
-    SP1HIP_REQUIRE(max_log_row_count >= 0 && max_log_row_count <= 30, "max_log_row_count out of range");
-    const uint64_t M = (uint64_t)1 << max_log_row_count;
-    // only tables with real rows go to the dense PCS (prover.rs:L129-L131); all of them are counted
-    std::vector<sp1hip_table_t> dense;
-    std::vector<uint64_t> rows, cols;
-    for (int i = 0; i < n_tables; i++) {
-        SP1HIP_REQUIRE(tables[i].rows <= M, "table taller than 2^max_log_row_count");
-        rows.push_back(tables[i].rows);
-        cols.push_back(tables[i].cols);
-        if (tables[i].rows) dense.push_back(tables[i]);
-    }
+    SP1HIP_REQUIRE(h_commit && out, "bad argument");
+    JaggedTables t;
+    SP1HIP_TRY(jagged_select_tables(tables, n_tables, max_log_row_count, &t));
     uint32_t inner[8];
     uint64_t added = 0;
-    SP1HIP_TRY(sp1hip_stacked_commit(dense.data(), (int)dense.size(), log_stacking_height, batch_size, lg_blowup, inner,
+    SP1HIP_TRY(sp1hip_stacked_commit(t.dense.data(), (int)t.dense.size(), log_stacking_height, batch_size, lg_blowup, inner,
                                      &added, out, stream));
-    // two dummy tables account for the stacking padding (prover.rs:L133-L139)
-    uint64_t added_cols = (added + M - 1) / M;
-    if (added_cols < 1) added_cols = 1;
-    rows.push_back(M);
-    rows.push_back(added - (added_cols - 1) * M);
-    cols.push_back(added_cols - 1);
-    cols.push_back(1);
-    std::vector<uint32_t> meta;
-    meta.push_back(kb::to_monty((uint32_t)rows.size()));
-    for (uint64_t r : rows) meta.push_back(kb::to_monty((uint32_t)r));
-    for (uint64_t c : cols) meta.push_back(kb::to_monty((uint32_t)c));
+    std::vector<uint32_t> meta = jagged_finish_counts(added, max_log_row_count, std::move(t), *out);
+    for (uint32_t& x : meta) x = kb::to_monty(x);
     uint32_t h[8];
     host_hash(meta, h);
     host_compress(inner, h, h_commit);
-    // what the evaluation proof (jagged.hip) needs later: JaggedProverData (prover.rs:L150-L156)
-    (*out)->jagged = true;
-    (*out)->max_log_row_count = max_log_row_count;
-    (*out)->row_counts = rows;
-    (*out)->column_counts = cols;
-    (*out)->padding_column_count = added_cols;
     memcpy((*out)->jagged_commit, h_commit, 32);
     return SP1HIP_SUCCESS;
 }

@@ -274,11 +274,12 @@ typedef struct {
     int proof_of_work_bits;  /* core: 16 */
 } sp1hip_fri_config_t;
 
-/* `BasefoldProver::prove_trusted_mle_evaluations` (prover.rs:L102-L243). `rounds[r]` are the handles of
- * the commitment rounds in order; h_claims holds one ext per column flattened round -> mle -> column.
- * Writes the bincode encoding of `BasefoldProof` (/root/reference/slop/crates/basefold/src/verifier.rs:L94-L116)
- * into h_proof (capacity *proof_len on entry, size on return; SP1HIP_ERROR_BUFFER_TOO_SMALL sets the needed
- * size and leaves the challenger untouched). */
+/* `BasefoldProver::prove_trusted_mle_evaluations` (prover.rs:L102-L243). `rounds[r]` are the handles of the commitment rounds in
+ * order; h_claims holds one ext per column flattened round -> mle -> column. Writes the bincode encoding of `BasefoldProof`
+ * (/root/reference/slop/crates/basefold/src/verifier.rs:L94-L116) into h_proof (capacity *proof_len on entry, size on return;
+ * SP1HIP_ERROR_BUFFER_TOO_SMALL sets the needed size and leaves the challenger untouched). Malformed input (a round of another
+ * dimension or blowup, a claims count other than the total width, dim + log_blowup > 24, proof_of_work_bits >= 31) is
+ * SP1HIP_ERROR_INVALID_ARGUMENT before any device work and before the size protocol (a too-small buffer does not change that). */
 int sp1hip_basefold_prove(const sp1hip_ext_t* h_point, int dim, sp1hip_basefold_data_t* const* rounds, int n_rounds,
                           const sp1hip_ext_t* h_claims, size_t n_claims, sp1hip_fri_config_t config,
                           sp1hip_challenger_t* challenger, uint8_t* h_proof, size_t* proof_len,

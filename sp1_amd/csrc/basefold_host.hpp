@@ -1,7 +1,13 @@
-// sp1_amd/csrc/basefold_host.hpp — host-side pieces shared by the two BaseFold provers (prover.hip: the inner KoalaBear
-// Poseidon2 configuration; outer_basefold.hip: the outer BN254 one): the arena-backed device buffer, the bincode writer, the
-// batching coefficients, and the internal entry points of the field kernels (basefold.hip) both round loops launch.
+// sp1_amd/csrc/basefold_host.hpp — the seam between the BaseFold opening (prover.hip) and the configuration it runs under.
+// `BasefoldProver::prove_trusted_mle_evaluations` is field work — batching, the RS encode, the folds, the query gathers — around
+// what depends on the hash: the transcript, the tree of a fold round, the way opened digests leave Montgomery form and the bytes
+// of a digest. basefold_prove_with is the one round loop; the inner prover (prover.hip: KoalaBear Poseidon2, DuplexChallenger)
+// and the outer one (outer_basefold.hip: Poseidon2-BN254, MultiField32Challenger) are two BasefoldBackends. Also here: the
+// handle core both commits fill (BasefoldData), the arena-backed device buffer, the bincode writer, the batching coefficients,
+// and the internal entry points of the field kernels (basefold.hip) the loop launches.
 #pragma once
+#include <atomic>
+#include <memory>
 #include <vector>
 
 #include "device_ctx.hpp"
@@ -89,5 +95,68 @@ inline std::vector<kb::Ext> partial_lagrange_host(const std::vector<kb::Ext>& pt
     }
     return ev;
 }
+
+// ---------------------------------------------------------------- the committed round
+// `BasefoldProverData` (/root/reference/slop/crates/basefold-prover/src/prover.rs:L25-L31): what sp1hip_basefold_data_t and
+// sp1hip_outer_basefold_data_t are. Nothing in it depends on the hash: root and commit are 8 words either way (KoalaBear
+// Montgomery words inside, the Montgomery words of one BN254 element outside).
+struct BasefoldData {
+    int lg_n = 0, lg_blowup = 0;
+    std::vector<sp1hip_tensor_t> mles;            // caller-owned inputs [2^lg_n x w], column-major
+    std::vector<std::unique_ptr<DeviceBuf>> cws;  // codewords [2^(lg_n+lg_blowup) x w]
+    std::vector<sp1hip_tensor_t> cw_tensors;
+    DeviceBuf tree;
+    uint32_t root[8], commit[8];
+    uint32_t total_width = 0;
+    // The blocks go back to the free list of the stream that created them, which orders their reuse behind that stream's
+    // work only. A handle that was also read on ANOTHER stream (a proving key's preprocessed commitment is opened by every
+    // prover, each on its own stream) waits for the device before it lets go.
+    std::atomic<bool> foreign_use{false};
+    ~BasefoldData() { if (foreign_use) (void)hipDeviceSynchronize(); }
+};
+
+// The two halves of `commit_mles` that do not depend on the tree (prover.hip). basefold_data_alloc: the codewords and the tree
+// of a commitment to `mles` on s; fills mles, cws, cw_tensors and total_width. basefold_data_fetch_commit: the 16 words
+// [root | commit] the tree left at d_root_and_commit, through the mailbox into the handle and h_commit.
+int basefold_data_alloc(BasefoldData* pd, const sp1hip_tensor_t* mles, int n_mles, int lg_n, int lg_blowup, hipStream_t s);
+int basefold_data_fetch_commit(BasefoldData* pd, const uint32_t* d_root_and_commit, uint32_t h_commit[8], hipStream_t s);
+
+// ---------------------------------------------------------------- the opening
+enum BasefoldStage { BF_GRIND, BF_BATCH_ENCODE, BF_COMMIT_PHASE, BF_OPENINGS };
+
+struct BasefoldBackend {
+    virtual ~BasefoldBackend() {}
+    virtual const char* entry_point() const = 0;      // the C entry point, for messages
+    // the name a stage is timed under (sp1hip_timers_*); none: the stage records no events
+    virtual const char* stage_timer(BasefoldStage) const { return nullptr; }
+    // ---- transcript, in KoalaBear Montgomery words: the proof runs on a clone of the caller's challenger; accept() hands the
+    // state over on success
+    virtual int begin() = 0;
+    virtual void observe(uint32_t monty) = 0;
+    virtual kb::Ext sample_ext() = 0;
+    virtual uint32_t sample_bits(int bits) = 0;
+    virtual int observe_commitment(const uint32_t commit[8]) = 0;     // a fold round's commitment as the tree handed it over
+    virtual int grind(int bits, uint32_t* witness_monty, hipStream_t s) = 0;
+    virtual void accept() = 0;
+    // ---- the tree over the paired leaves of a fold round's codeword (commit_ext_pairs' contract: the last kernel publishes
+    // [d_publish_extra[0..4) | root | commitment] into the mailbox slot under sequence number publish_seq)
+    virtual int commit_pairs(const uint32_t* d_cw, int lg_c, uint32_t* d_tree, uint32_t* d_root_and_commit, hipStream_t s,
+                             const uint32_t* d_publish_extra, uint32_t* h_publish_slot, uint32_t publish_seq) = 0;
+    // ---- the finished opening buffer out of Montgomery form, in place: the values of every opening (KoalaBear words), and
+    // right behind them (d_paths == d_values + n_value_words) the path digests of every opening, 8 words each
+    virtual int openings_from_monty(uint32_t* d_values, size_t n_value_words, uint32_t* d_paths, size_t n_path_words, hipStream_t s) = 0;
+    // ---- the bincode of a digest
+    virtual size_t digest_bytes() const = 0;
+    virtual void write_digest(ByteWriter& w, const uint32_t* monty) const = 0;                           // roots, fri_commitments
+    virtual void write_path_digests(ByteWriter& w, const uint32_t* canonical, size_t n) const = 0;      // n opened path entries
+};
+
+// bincode(BasefoldProof) size with digests of digest_bytes each
+size_t basefold_proof_size(size_t digest_bytes, int dim, const uint32_t* round_widths, int n_rounds, const sp1hip_fri_config_t& cfg);
+
+// The argument checks, the size protocol (SP1HIP_ERROR_BUFFER_TOO_SMALL sets *proof_len), the proof, the bytes.
+int basefold_prove_with(BasefoldBackend& be, const sp1hip_ext_t* h_point, int dim, BasefoldData* const* rounds, int n_rounds,
+                        const sp1hip_ext_t* h_claims, size_t n_claims, sp1hip_fri_config_t config, uint8_t* h_proof, size_t* proof_len,
+                        sp1hip_stream_t stream);
 
 }  // namespace sp1hip

@@ -85,10 +85,10 @@ size_t arena_release_stream(hipStream_t stream);      // blocks cached for a str
 bool timers_on();
 int timer_begin(const char* name, hipStream_t s);      // index of the record, -1 if none
 void timer_end(int idx, hipStream_t s);
-struct ScopedTimer {
+struct ScopedTimer {              // a null name records nothing
     hipStream_t s;
     int idx;
-    ScopedTimer(const char* name, hipStream_t stream) : s(stream), idx(timers_on() ? timer_begin(name, stream) : -1) {}
+    ScopedTimer(const char* name, hipStream_t stream) : s(stream), idx(name && timers_on() ? timer_begin(name, stream) : -1) {}
     ~ScopedTimer() { if (idx >= 0) timer_end(idx, s); }
 };
 

@@ -5,10 +5,12 @@
 //   sp1hip::DuplexChallenger      `DuplexChallenger<KoalaBear, KoalaPerm, 16, 8>` via `IopCtx::Challenger`
 //                                 (/root/reference/slop/crates/challenger/src/lib.rs:L25-L87; semantics as
 //                                 restated in /root/reference/sp1-gpu/crates/sys/include/challenger/challenger.cuh:L13-L118)
-//   sp1hip::BasefoldProverData    `BasefoldProverData` (/root/reference/slop/crates/basefold-prover/src/prover.rs:L25-L31)
+//   sp1hip::BasefoldData          `BasefoldProverData` (/root/reference/slop/crates/basefold-prover/src/prover.rs:L25-L31)
 //   sp1hip::commit_mles           `BasefoldProver::commit_mles`                  (prover.rs:L78-L99)
-//   sp1hip::prove_trusted_mle_evaluations  `BasefoldProver::prove_trusted_mle_evaluations` (prover.rs:L102-L243)
+//   sp1hip::basefold_prove_with   `BasefoldProver::prove_trusted_mle_evaluations` (prover.rs:L102-L243)
 //       -> FriCpuProver::batch / commit_phase_round (/root/reference/slop/crates/basefold-prover/src/fri.rs:L31-L129)
+//       the ONE round loop of both configurations, over a BasefoldBackend (basefold_host.hpp): the InnerBasefoldBackend here
+//       (DuplexChallenger, KoalaBear Poseidon2 trees, 32-byte digests), the OuterBasefoldBackend in outer_basefold.hip
 //   bincode writer                `BasefoldProof` (/root/reference/slop/crates/basefold/src/verifier.rs:L94-L116),
 //                                 `MerkleTreeOpeningAndProof`/`MerkleTreeTcsProof` (/root/reference/slop/crates/merkle-tree/src/tcs.rs:L49-L91)
 //
@@ -16,8 +18,8 @@
 // kernel on the caller's stream. One host<->device sync per fold round (16 B + 32 B read back).
 // PoW witnesses: the SMALLEST valid witness is returned (the reference's rayon `find_any` returns
 // any valid one).
-#include <atomic>
 #include <algorithm>
+#include <array>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -139,20 +141,7 @@ static int grind(DuplexChallenger& ch, int bits, uint32_t* witness_monty, hipStr
 
 struct sp1hip_challenger_s { sp1hip::DuplexChallenger ch; };
 
-struct sp1hip_basefold_data_s {
-    int lg_n = 0, lg_blowup = 0;
-    std::vector<sp1hip_tensor_t> mles;                    // caller-owned inputs [2^lg_n x w], column-major
-    std::vector<std::unique_ptr<sp1hip::DeviceBuf>> cws;  // codewords [2^(lg_n+lg_blowup) x w]
-    std::vector<sp1hip_tensor_t> cw_tensors;
-    sp1hip::DeviceBuf tree;
-    uint32_t root[8], commit[8];
-    uint32_t total_width = 0;
-    // The blocks go back to the free list of the stream that created them, which orders their reuse behind that stream's
-    // work only. A handle that was also read on ANOTHER stream (a proving key's preprocessed commitment is opened by every
-    // prover, each on its own stream) waits for the device before it lets go.
-    std::atomic<bool> foreign_use{false};
-    ~sp1hip_basefold_data_s() { if (foreign_use) (void)hipDeviceSynchronize(); }
-};
+struct sp1hip_basefold_data_s : sp1hip::BasefoldData {};
 
 namespace sp1hip {
 
@@ -177,60 +166,59 @@ void challenger_import(sp1hip_challenger_t* ch, const uint32_t* w) {
     ch->ch.n_out = (int)w[33];
 }
 
-// values / paths: CANONICAL words (the query phase converts the whole opening buffer on the device before it leaves)
-static void write_opening(ByteWriter& w, const uint32_t* values, size_t n_values, size_t n_idx, size_t width,
-                          const uint32_t* root, size_t lg_h, const uint32_t* paths, size_t n_paths) {
+// values / paths: CANONICAL words (the query phase converts the whole opening buffer on the device before it leaves); root:
+// Montgomery words
+static void write_opening(const BasefoldBackend& be, ByteWriter& w, const uint32_t* values, size_t n_values, size_t n_idx,
+                          size_t width, const uint32_t* root, size_t lg_h, const uint32_t* paths) {
     w.u64(n_values);
     w.canonical_words(values, n_values);
     w.u64(2); w.u64(n_idx); w.u64(width);
-    w.felts(root, 8);
+    be.write_digest(w, root);
     w.u64(lg_h);
     w.u64(width);
     w.u64(n_idx * lg_h);
-    w.canonical_words(paths, n_paths);
+    be.write_path_digests(w, paths, n_idx * lg_h);
     w.u64(2); w.u64(n_idx); w.u64(lg_h);
 }
 
-static size_t opening_size(size_t n_idx, size_t width, size_t lg_h) {
-    return 8 + 4 * n_idx * width + 24 + 32 + 8 + 8 + 8 + 32 * n_idx * lg_h + 24;
+static size_t opening_size(size_t digest_bytes, size_t n_idx, size_t width, size_t lg_h) {
+    return 8 + 4 * n_idx * width + 24 + digest_bytes + 8 + 8 + 8 + digest_bytes * n_idx * lg_h + 24;
 }
 
-static size_t proof_size(int dim, const std::vector<uint32_t>& widths, const sp1hip_fri_config_t& cfg) {
-    size_t q = (size_t)cfg.num_queries;
-    size_t sz = 8 + (size_t)dim * 32 + 8 + (size_t)dim * 32 + 8;
-    for (uint32_t w : widths) sz += opening_size(q, w, (size_t)dim + cfg.log_blowup);
+size_t basefold_proof_size(size_t digest_bytes, int dim, const uint32_t* widths, int n_rounds, const sp1hip_fri_config_t& cfg) {
+    const size_t q = (size_t)cfg.num_queries;
+    size_t sz = 8 + (size_t)dim * 32 + 8 + (size_t)dim * digest_bytes + 8;
+    for (int r = 0; r < n_rounds; r++) sz += opening_size(digest_bytes, q, widths[r], (size_t)dim + cfg.log_blowup);
     sz += 8;
-    for (int r = 0; r < dim; r++) sz += opening_size(q, 8, (size_t)dim + cfg.log_blowup - 1 - r);
+    for (int r = 0; r < dim; r++) sz += opening_size(digest_bytes, q, 8, (size_t)dim + cfg.log_blowup - 1 - r);
     return sz + 16 + 4 + 4;
 }
 
-static int prove_trusted_mle_evaluations(std::vector<kb::Ext> point, sp1hip_basefold_data_s* const* rounds, int n_rounds,
-                                         const kb::Ext* claims, size_t n_claims, const sp1hip_fri_config_t& cfg,
-                                         DuplexChallenger& ch, uint8_t* out, size_t out_cap, size_t* out_len, hipStream_t s) {
+// The checked instance on the backend's working transcript: the proof into `out` (capacity out_cap).
+static int prove_trusted_mle_evaluations(BasefoldBackend& be, std::vector<kb::Ext> point, BasefoldData* const* rounds, int n_rounds,
+                                         const kb::Ext* claims, size_t n_claims, const sp1hip_fri_config_t& cfg, uint8_t* out,
+                                         size_t out_cap, size_t* out_len, hipStream_t s) {
     const int dim = (int)point.size();
     const int lb = cfg.log_blowup;
     const size_t nq = (size_t)cfg.num_queries;
     // all mles of all rounds, in order
     std::vector<sp1hip_tensor_t> mles;
-    for (int r = 0; r < n_rounds; r++) {
-        SP1HIP_REQUIRE(rounds[r]->lg_n == dim, "eval point dimension mismatch");
-        SP1HIP_REQUIRE(rounds[r]->lg_blowup == lb, "round committed with a different blowup");
+    for (int r = 0; r < n_rounds; r++)
         for (auto& m : rounds[r]->mles) mles.push_back(m);
-    }
-    size_t total_len = 0;
-    for (auto& m : mles) total_len += m.width;
-    SP1HIP_REQUIRE(total_len == n_claims, "one evaluation claim per committed column expected");
-    SP1HIP_REQUIRE(dim >= 1, "at least one variable expected");
-    SP1HIP_REQUIRE(dim + lb <= kb::TWO_ADICITY, "instance exceeds two-adicity");
+    const size_t total_len = n_claims;
+    const auto observe_ext = [&](const kb::Ext& e) { for (int k = 0; k < 4; k++) be.observe(e.c[k]); };
 
     ByteWriter w;
     w.p = out;
     w.cap = out_cap;
     // Grind for batch randomness, then the batching coefficients.
-    uint32_t batch_witness;
-    SP1HIP_TRY(grind(ch, 5, &batch_witness, s));
+    uint32_t batch_witness, pow_witness;
+    {
+        ScopedTimer t(be.stage_timer(BF_GRIND), s);
+        SP1HIP_TRY(be.grind(5, &batch_witness, s));
+    }
     std::vector<kb::Ext> bpt(log2_ceil(total_len));
-    for (auto& x : bpt) x = ch.sample_ext();
+    for (auto& x : bpt) x = be.sample_ext();
     std::vector<kb::Ext> coeffs = partial_lagrange_host(bpt);
 
     const size_t n = (size_t)1 << dim, N0 = n << lb;
@@ -243,23 +231,24 @@ static int prove_trusted_mle_evaluations(std::vector<kb::Ext> point, sp1hip_base
     SP1HIP_TRY(mb.init(s));
     PinnedStage stage;
     SP1HIP_TRY(stage.init(s));
-    SP1HIP_TRY(stage.upload(d_coeffs.p, coeffs.data(), total_len * 16));
-    SP1HIP_TRY(sp1hip_basefold_batch(mles.data(), (int)mles.size(), dim, d_coeffs.u32(), d_mle[0].u32(), s));
+    // codewords of every round are kept for the query phase: sizes N0, N0/2, ..., 2 (ext SoA)
+    std::vector<std::unique_ptr<DeviceBuf>> cws, trees;
+    {
+        ScopedTimer t(be.stage_timer(BF_BATCH_ENCODE), s);
+        SP1HIP_TRY(stage.upload(d_coeffs.p, coeffs.data(), total_len * 16));
+        SP1HIP_TRY(sp1hip_basefold_batch(mles.data(), (int)mles.size(), dim, d_coeffs.u32(), d_mle[0].u32(), s));
+        cws.emplace_back(new DeviceBuf());
+        SP1HIP_TRY(cws.back()->alloc(N0 * 16, s));
+        SP1HIP_TRY(sp1hip_rs_encode_batch(cws.back()->u32(), d_mle[0].u32(), dim, lb, 4, s));
+    }
     kb::Ext cur_claim = kb::ext_zero();
     for (size_t i = 0; i < n_claims; i++) cur_claim = kb::ext_add(cur_claim, kb::ext_mul(claims[i], coeffs[i]));
 
-    // codewords of every round are kept for the query phase: sizes N0, N0/2, ..., 2 (ext SoA)
-    std::vector<std::unique_ptr<DeviceBuf>> cws, trees;
-    cws.emplace_back(new DeviceBuf());
-    SP1HIP_TRY(cws.back()->alloc(N0 * 16, s));
-    SP1HIP_TRY(sp1hip_rs_encode_batch(cws.back()->u32(), d_mle[0].u32(), dim, lb, 4, s));
-
-    ch.observe(kb::to_monty((uint32_t)dim));
+    be.observe(kb::to_monty((uint32_t)dim));
     DeviceBuf d_rb;  // [0..4) zero_val, [4..20) root+commit, [20..24) final poly
     SP1HIP_TRY(d_rb.alloc(24 * 4, s));
-    std::vector<std::array<uint32_t, 8>> round_roots;
+    std::vector<std::array<uint32_t, 8>> round_roots, fri_commitments;
     std::vector<kb::Ext> uni;
-    std::vector<std::array<uint32_t, 8>> fri_commitments;
     int cur = 0;
     SP1HIP_TRY(eq_prefix_tables_soa_async(point.data(), dim - 1, d_eq.u32(), s));
     auto eq_table = [&](int t) { return d_eq.u32() + 4 * (((size_t)1 << t) - 1); };     // eq over the first t coordinates
@@ -276,34 +265,37 @@ static int prove_trusted_mle_evaluations(std::vector<kb::Ext> point, sp1hip_base
     }
     // zero_val of round 0 = sum_i eq(point', i) * mle[2 i]; every later round's comes out of the fold before it
     SP1HIP_TRY(ext_fixed_at_zero_async(d_mle[cur].u32(), dim, eq_table(dim - 1), d_rb.u32(), s));
-    for (int r = 0; r < dim; r++) {
-        const int lg_m = dim - r;             // current mle has 2^lg_m entries
-        const int lg_c = lg_m + lb;           // current codeword has 2^lg_c entries
-        kb::Ext last = point.back();
-        point.pop_back();
-        // commit to the paired leaves of the current codeword; the tree's last kernel hands [zero_val | root | commitment]
-        // to the host
-        SP1HIP_TRY(commit_ext_pairs(cws[r]->u32(), lg_c, trees[r]->u32(), d_rb.u32() + 4, s, d_rb.u32(), mb.h_slot, mb.seq + 1));
-        uint32_t rb[20];
-        SP1HIP_TRY(mb.wait_next(rb, 20));
-        kb::Ext zero_val{{rb[0], rb[1], rb[2], rb[3]}};
-        kb::Ext one_val = kb::ext_add(kb::ext_mul(kb::ext_sub(cur_claim, zero_val), kb::ext_inv(last)), zero_val);
-        uni.push_back(zero_val);
-        uni.push_back(one_val);
-        ch.observe_ext(zero_val);
-        ch.observe_ext(one_val);
-        std::array<uint32_t, 8> root, commit;
-        memcpy(root.data(), rb + 4, 32);
-        memcpy(commit.data(), rb + 12, 32);
-        round_roots.push_back(root);
-        fri_commitments.push_back(commit);
-        ch.observe_slice(commit.data(), 8);
-        kb::Ext beta = ch.sample_ext();
-        // both folds and the next round's zero_val partials in one launch
-        SP1HIP_TRY(fold_round_async(cws[r]->u32(), lg_c, d_mle[cur].u32(), lg_m, beta, cws[r + 1]->u32(),
-                                    d_mle[cur ^ 1].u32(), lg_m >= 2 ? eq_table(lg_m - 2) : nullptr, d_rb.u32(), d_fold_partial.u32(), s));
-        cur ^= 1;
-        cur_claim = kb::ext_add(zero_val, kb::ext_mul(beta, one_val));
+    {
+        ScopedTimer t(be.stage_timer(BF_COMMIT_PHASE), s);
+        for (int r = 0; r < dim; r++) {
+            const int lg_m = dim - r;             // current mle has 2^lg_m entries
+            const int lg_c = lg_m + lb;           // current codeword has 2^lg_c entries
+            kb::Ext last = point.back();
+            point.pop_back();
+            // commit to the paired leaves of the current codeword; the tree's last kernel hands [zero_val | root | commitment]
+            // to the host
+            SP1HIP_TRY(be.commit_pairs(cws[r]->u32(), lg_c, trees[r]->u32(), d_rb.u32() + 4, s, d_rb.u32(), mb.h_slot, mb.seq + 1));
+            uint32_t rb[20];
+            SP1HIP_TRY(mb.wait_next(rb, 20));
+            kb::Ext zero_val{{rb[0], rb[1], rb[2], rb[3]}};
+            kb::Ext one_val = kb::ext_add(kb::ext_mul(kb::ext_sub(cur_claim, zero_val), kb::ext_inv(last)), zero_val);
+            uni.push_back(zero_val);
+            uni.push_back(one_val);
+            observe_ext(zero_val);
+            observe_ext(one_val);
+            std::array<uint32_t, 8> root, commit;
+            memcpy(root.data(), rb + 4, 32);
+            memcpy(commit.data(), rb + 12, 32);
+            round_roots.push_back(root);
+            fri_commitments.push_back(commit);
+            SP1HIP_TRY(be.observe_commitment(commit.data()));
+            kb::Ext beta = be.sample_ext();
+            // both folds and the next round's zero_val partials in one launch
+            SP1HIP_TRY(fold_round_async(cws[r]->u32(), lg_c, d_mle[cur].u32(), lg_m, beta, cws[r + 1]->u32(), d_mle[cur ^ 1].u32(),
+                                        lg_m >= 2 ? eq_table(lg_m - 2) : nullptr, d_rb.u32(), d_fold_partial.u32(), s));
+            cur ^= 1;
+            cur_claim = kb::ext_add(zero_val, kb::ext_mul(beta, one_val));
+        }
     }
     // final_poly = first ext element of the last codeword (length 2^lb)
     {
@@ -314,67 +306,71 @@ static int prove_trusted_mle_evaluations(std::vector<kb::Ext> point, sp1hip_base
     uint32_t fp[4];
     SP1HIP_TRY(mb.fetch(d_rb.u32() + 20, 4, fp));
     kb::Ext final_poly{{fp[0], fp[1], fp[2], fp[3]}};
-    ch.observe_ext(final_poly);
-    uint32_t pow_witness;
-    SP1HIP_TRY(grind(ch, cfg.proof_of_work_bits, &pow_witness, s));
+    observe_ext(final_poly);
+    {
+        ScopedTimer t(be.stage_timer(BF_GRIND), s);
+        SP1HIP_TRY(be.grind(cfg.proof_of_work_bits, &pow_witness, s));
+    }
     std::vector<uint32_t> q(nq);
-    for (auto& x : q) x = ch.sample_bits(dim + lb);
+    for (auto& x : q) x = be.sample_bits(dim + lb);
 
     // ---- serialise: univariate messages, commitments, openings
     w.u64((uint64_t)dim);
     for (auto& e : uni) w.ext(e);
     w.u64((uint64_t)dim);
-    for (auto& c : fri_commitments) w.felts(c.data(), 8);
+    for (auto& c : fri_commitments) be.write_digest(w, c.data());
 
     // Query phase: every opening (component rounds, then the dim fold rounds) is produced into ONE device buffer and
-    // brought back with one copy and one synchronise instead of one round trip per opening.
-    DeviceBuf d_idx, d_open;
+    // brought back with one copy and one synchronise instead of one round trip per opening. The values of all openings come
+    // first (KoalaBear words), then the paths of all openings (digests): each region leaves Montgomery form in its own way.
     struct Slot { size_t vals_off, n_vals, paths_off, n_paths; };
     std::vector<Slot> slots;
-    size_t words = 0;
+    size_t n_val_words = 0, n_path_words = 0;
     for (int r = 0; r < n_rounds; r++) {
-        const size_t nv = nq * rounds[r]->total_width, np = nq * (size_t)(dim + lb) * 8;
-        slots.push_back(Slot{words, nv, words + nv, np});
-        words += nv + np;
+        slots.push_back(Slot{n_val_words, nq * rounds[r]->total_width, n_path_words, nq * (size_t)(dim + lb) * 8});
+        n_val_words += slots.back().n_vals;
+        n_path_words += slots.back().n_paths;
     }
     for (int r = 0; r < dim; r++) {
-        const size_t lg_h = (size_t)(dim + lb - r - 1);
-        const size_t nv = nq * 8, np = nq * lg_h * 8;
-        slots.push_back(Slot{words, nv, words + nv, np});
-        words += nv + np;
+        slots.push_back(Slot{n_val_words, nq * 8, n_path_words, nq * (size_t)(dim + lb - r - 1) * 8});
+        n_val_words += slots.back().n_vals;
+        n_path_words += slots.back().n_paths;
     }
+    for (auto& sl : slots) sl.paths_off += n_val_words;
+    const size_t words = n_val_words + n_path_words;
+    SP1HIP_REQUIRE(words < ((size_t)1 << 32), "opening buffer too large");
+    ScopedTimer t_open(be.stage_timer(BF_OPENINGS), s);
+    DeviceBuf d_idx, d_open, d_descs;
     SP1HIP_TRY(d_idx.alloc(nq * 4, s));
     SP1HIP_TRY(d_open.alloc(std::max<size_t>(words, 1) * 4, s));
     SP1HIP_TRY(stage.upload(d_idx.p, q.data(), nq * 4));
     for (int r = 0; r < n_rounds; r++) {
-        sp1hip_basefold_data_s* pd = rounds[r];
+        BasefoldData* pd = rounds[r];
         const Slot& sl = slots[r];
-        SP1HIP_TRY(sp1hip_merkle_open(pd->cw_tensors.data(), (int)pd->cw_tensors.size(), dim + lb, pd->tree.u32(), d_idx.u32(),
-                                      nq, d_open.u32() + sl.vals_off, d_open.u32() + sl.paths_off, s));
+        SP1HIP_TRY(sp1hip_merkle_open(pd->cw_tensors.data(), (int)pd->cw_tensors.size(), dim + lb, pd->tree.u32(), d_idx.u32(), nq,
+                                      d_open.u32() + sl.vals_off, d_open.u32() + sl.paths_off, s));
     }
     {   // every fold round's pairs and paths in one launch
-        SP1HIP_REQUIRE(words < ((size_t)1 << 32), "opening buffer too large");
         std::vector<FoldOpenDesc> descs(dim);
         for (int r = 0; r < dim; r++) {
             const Slot& sl = slots[n_rounds + r];
             descs[r] = FoldOpenDesc{cws[r]->u32(), trees[r]->u32(), (uint32_t)(dim + lb - r), (uint32_t)sl.vals_off, (uint32_t)sl.paths_off, 0u};
         }
-        DeviceBuf d_descs;
         SP1HIP_TRY(d_descs.alloc(descs.size() * sizeof(FoldOpenDesc), s));
         SP1HIP_TRY(stage.upload(d_descs.p, descs.data(), descs.size() * sizeof(FoldOpenDesc)));
         SP1HIP_TRY(open_fold_rounds(reinterpret_cast<const FoldOpenDesc*>(d_descs.p), dim, dim + lb, d_idx.u32(), nq, d_open.u32(), s));
     }
-    // The opening buffer leaves the device as CANONICAL words (one conversion launch instead of ~340k host reductions) and
+    // The opening buffer leaves the device as CANONICAL words (conversion launches instead of ~340k host reductions) and
     // lands in a pinned block when it fits one (no pageable bounce, no stream synchronise: the mailbox fence below orders
     // the host behind the copy).
-    SP1HIP_TRY(sp1hip_from_monty(d_open.u32(), words, (sp1hip_stream_t)s));
+    SP1HIP_TRY(be.openings_from_monty(d_open.u32(), n_val_words, d_open.u32() + n_val_words, n_path_words, s));
     std::vector<uint32_t> opened_pageable;
     PinnedBlock dl{nullptr};
     struct Release { PinnedBlock* b; ~Release() { if (b->h) pinned_stage_release(*b); } } release{&dl};
     const uint32_t* opened = nullptr;
     if (words * 4 <= PINNED_STAGE_BYTES && pinned_stage_acquire(&dl) == SP1HIP_SUCCESS) {
         SP1HIP_HIP(hipMemcpyAsync(dl.h, d_open.p, words * 4, hipMemcpyDeviceToHost, s));
-        SP1HIP_TRY(mb.fetch(nullptr, 0, nullptr));             // (its completion also covers the q upload above)
+        SP1HIP_TRY(mb.fetch(nullptr, 0, nullptr));             // (its completion also covers the uploads above)
         opened = reinterpret_cast<const uint32_t*>(dl.h);
     } else {
         dl.h = nullptr;
@@ -386,12 +382,12 @@ static int prove_trusted_mle_evaluations(std::vector<kb::Ext> point, sp1hip_base
     w.u64((uint64_t)n_rounds);
     for (int r = 0; r < n_rounds; r++) {
         const Slot& sl = slots[r];
-        write_opening(w, opened + sl.vals_off, sl.n_vals, nq, rounds[r]->total_width, rounds[r]->root, (size_t)(dim + lb), opened + sl.paths_off, sl.n_paths);
+        write_opening(be, w, opened + sl.vals_off, sl.n_vals, nq, rounds[r]->total_width, rounds[r]->root, (size_t)(dim + lb), opened + sl.paths_off);
     }
     w.u64((uint64_t)dim);
     for (int r = 0; r < dim; r++) {
         const Slot& sl = slots[n_rounds + r];
-        write_opening(w, opened + sl.vals_off, sl.n_vals, nq, 8, round_roots[r].data(), (size_t)(dim + lb - r - 1), opened + sl.paths_off, sl.n_paths);
+        write_opening(be, w, opened + sl.vals_off, sl.n_vals, nq, 8, round_roots[r].data(), (size_t)(dim + lb - r - 1), opened + sl.paths_off);
     }
     w.ext(final_poly);
     w.felt(pow_witness);
@@ -400,6 +396,74 @@ static int prove_trusted_mle_evaluations(std::vector<kb::Ext> point, sp1hip_base
     *out_len = w.n;
     return SP1HIP_SUCCESS;
 }
+
+int basefold_prove_with(BasefoldBackend& be, const sp1hip_ext_t* h_point, int dim, BasefoldData* const* rounds, int n_rounds,
+                        const sp1hip_ext_t* h_claims, size_t n_claims, sp1hip_fri_config_t config, uint8_t* h_proof, size_t* proof_len,
+                        sp1hip_stream_t stream) {
+    SP1HIP_REQUIRE(h_point && rounds && n_rounds > 0 && h_claims && proof_len, "null argument");
+    SP1HIP_REQUIRE(dim >= 1 && dim <= kb::TWO_ADICITY, "dim out of range");
+    SP1HIP_REQUIRE(config.num_queries > 0 && config.log_blowup >= 0 && config.proof_of_work_bits >= 0 && config.proof_of_work_bits < 31,
+                   "bad config");
+    SP1HIP_REQUIRE(dim + config.log_blowup <= kb::TWO_ADICITY, "instance exceeds two-adicity");
+    std::vector<uint32_t> widths;
+    size_t total_len = 0;
+    for (int r = 0; r < n_rounds; r++) {
+        SP1HIP_REQUIRE(rounds[r], "null round");
+        SP1HIP_REQUIRE(rounds[r]->lg_n == dim, "eval point dimension mismatch");
+        SP1HIP_REQUIRE(rounds[r]->lg_blowup == config.log_blowup, "round committed with a different blowup");
+        widths.push_back(rounds[r]->total_width);
+        total_len += rounds[r]->total_width;
+    }
+    SP1HIP_REQUIRE(total_len == n_claims, "one evaluation claim per committed column expected");
+    for (int r = 0; r < n_rounds; r++)
+        if (rounds[r]->tree.s != S(stream)) rounds[r]->foreign_use = true;
+    const size_t need = basefold_proof_size(be.digest_bytes(), dim, widths.data(), n_rounds, config);
+    if (!h_proof || *proof_len < need) {
+        *proof_len = need;
+        set_error("%s: proof buffer too small, need %zu bytes", be.entry_point(), need);
+        return SP1HIP_ERROR_BUFFER_TOO_SMALL;
+    }
+    std::vector<kb::Ext> point(dim);
+    memcpy(point.data(), h_point, (size_t)dim * 16);
+    SP1HIP_TRY(be.begin());                // work on a copy of the transcript; commit it only on success
+    size_t written = 0;
+    SP1HIP_TRY(prove_trusted_mle_evaluations(be, point, rounds, n_rounds, reinterpret_cast<const kb::Ext*>(h_claims), n_claims, config,
+                                             h_proof, need, &written, S(stream)));      // written in place
+    if (written != need) {
+        set_error("internal error: proof size %zu != expected %zu", written, need);
+        return SP1HIP_ERROR_RUNTIME;
+    }
+    *proof_len = written;
+    be.accept();
+    return SP1HIP_SUCCESS;
+}
+
+namespace {
+struct InnerBasefoldBackend final : BasefoldBackend {
+    DuplexChallenger& caller;
+    DuplexChallenger ch;
+    explicit InnerBasefoldBackend(DuplexChallenger& c) : caller(c) {}
+    const char* entry_point() const override { return "sp1hip_basefold_prove"; }
+    int begin() override { ch = caller; return SP1HIP_SUCCESS; }
+    void observe(uint32_t monty) override { ch.observe(monty); }
+    kb::Ext sample_ext() override { return ch.sample_ext(); }
+    uint32_t sample_bits(int bits) override { return ch.sample_bits(bits); }
+    int observe_commitment(const uint32_t commit[8]) override { ch.observe_slice(commit, 8); return SP1HIP_SUCCESS; }
+    int grind(int bits, uint32_t* witness_monty, hipStream_t s) override { return sp1hip::grind(ch, bits, witness_monty, s); }
+    void accept() override { caller = ch; }
+    int commit_pairs(const uint32_t* d_cw, int lg_c, uint32_t* d_tree, uint32_t* d_root_and_commit, hipStream_t s,
+                     const uint32_t* d_publish_extra, uint32_t* h_publish_slot, uint32_t publish_seq) override {
+        return commit_ext_pairs(d_cw, lg_c, d_tree, d_root_and_commit, s, d_publish_extra, h_publish_slot, publish_seq);
+    }
+    // digests are KoalaBear words like the values: one launch over the whole buffer
+    int openings_from_monty(uint32_t* d_values, size_t n_value_words, uint32_t*, size_t n_path_words, hipStream_t s) override {
+        return sp1hip_from_monty(d_values, n_value_words + n_path_words, (sp1hip_stream_t)s);
+    }
+    size_t digest_bytes() const override { return 32; }          // [KoalaBear; 8]
+    void write_digest(ByteWriter& w, const uint32_t* monty) const override { w.felts(monty, 8); }
+    void write_path_digests(ByteWriter& w, const uint32_t* canonical, size_t n) const override { w.canonical_words(canonical, 8 * n); }
+};
+}  // namespace
 
 }  // namespace sp1hip
 
@@ -471,6 +535,31 @@ int sp1hip_challenger_state(const sp1hip_challenger_t* ch, uint32_t* out34) {
 }  // extern "C"
 
 namespace sp1hip {
+int basefold_data_alloc(BasefoldData* pd, const sp1hip_tensor_t* mles, int n_mles, int lg_n, int lg_blowup, hipStream_t s) {
+    pd->lg_n = lg_n;
+    pd->lg_blowup = lg_blowup;
+    const size_t N = (size_t)1 << (lg_n + lg_blowup);
+    for (int i = 0; i < n_mles; i++) {
+        pd->mles.push_back(mles[i]);
+        pd->cws.emplace_back(new DeviceBuf());
+        SP1HIP_TRY(pd->cws.back()->alloc(N * mles[i].width * 4, s));
+        pd->cw_tensors.push_back({pd->cws.back()->u32(), mles[i].width});
+        pd->total_width += mles[i].width;
+    }
+    return pd->tree.alloc((2 * N - 1) * 32, s);
+}
+
+int basefold_data_fetch_commit(BasefoldData* pd, const uint32_t* d_root_and_commit, uint32_t h_commit[8], hipStream_t s) {
+    uint32_t h[16];
+    Mailbox mb;
+    SP1HIP_TRY(mb.init(s));
+    SP1HIP_TRY(mb.fetch(d_root_and_commit, 16, h));
+    memcpy(pd->root, h, 32);
+    memcpy(pd->commit, h + 8, 32);
+    memcpy(h_commit, pd->commit, 32);
+    return SP1HIP_SUCCESS;
+}
+
 // sp1hip_commit_mles with a hook: `before_encode(i, stream)` is called right before message i is encoded, on the stream
 // that encodes it — the stacked commit fills message i's slice of its dense buffer there (stacked.hip), so that with the
 // encodes on the side stream the 1.6 GB of table -> dense copies of a core shard run under the leaf hashes of the
@@ -483,19 +572,10 @@ int commit_mles_hooked(const sp1hip_tensor_t* mles, int n_mles, int lg_n, int lg
     const DeviceCtx* ctx;
     SP1HIP_TRY(get_device_ctx(&ctx));   // also configures the memory pool before the first allocation
     std::unique_ptr<sp1hip_basefold_data_s> pd(new sp1hip_basefold_data_s());
-    pd->lg_n = lg_n;
-    pd->lg_blowup = lg_blowup;
+    for (int i = 0; i < n_mles; i++) SP1HIP_REQUIRE(mles[i].d_data || mles[i].width == 0, "null mle");
+    SP1HIP_TRY(basefold_data_alloc(pd.get(), mles, n_mles, lg_n, lg_blowup, s));
     const int lg_h = lg_n + lg_blowup;
     const size_t N = (size_t)1 << lg_h;
-    for (int i = 0; i < n_mles; i++) {
-        SP1HIP_REQUIRE(mles[i].d_data || mles[i].width == 0, "null mle");
-        pd->mles.push_back(mles[i]);
-        pd->cws.emplace_back(new DeviceBuf());
-        SP1HIP_TRY(pd->cws.back()->alloc(N * mles[i].width * 4, s));
-        pd->cw_tensors.push_back({pd->cws.back()->u32(), mles[i].width});
-        pd->total_width += mles[i].width;
-    }
-    SP1HIP_TRY(pd->tree.alloc((2 * N - 1) * 32, s));
     DeviceBuf rc;
     SP1HIP_TRY(rc.alloc(64, s));
     // default: overlap when the codeword is large enough to fill the chip; "0" never, "1" always (tests)
@@ -534,14 +614,8 @@ int commit_mles_hooked(const sp1hip_tensor_t* mles, int n_mles, int lg_n, int lg
                                           (uint32_t)N, carry.u32(), pd->tree.u32(), ctx, s));
             }
             SP1HIP_TRY(merkle_finish_tree(pd->tree.u32(), lg_h, tw, rc.u32(), ctx, s));
-            uint32_t h[16];
-            Mailbox mb;
-            SP1HIP_TRY(mb.init(s));
-            SP1HIP_TRY(mb.fetch(rc.p, 16, h));              // `s` waited for every encode: `aux` is idle here
-            memcpy(pd->root, h, 32);
-            memcpy(pd->commit, h + 8, 32);
+            SP1HIP_TRY(basefold_data_fetch_commit(pd.get(), rc.u32(), h_commit, s));    // `s` waited for every encode: `aux` is idle here
         }
-        memcpy(h_commit, pd->commit, 32);
         *out = pd.release();
         return SP1HIP_SUCCESS;
     }
@@ -550,13 +624,7 @@ int commit_mles_hooked(const sp1hip_tensor_t* mles, int n_mles, int lg_n, int lg
         SP1HIP_TRY(sp1hip_rs_encode_batch(pd->cws[i]->u32(), mles[i].d_data, lg_n, lg_blowup, mles[i].width, s));
     }
     SP1HIP_TRY(sp1hip_merkle_commit(pd->cw_tensors.data(), n_mles, lg_h, pd->tree.u32(), rc.u32(), s));
-    uint32_t h[16];
-    Mailbox mb;
-    SP1HIP_TRY(mb.init(s));
-    SP1HIP_TRY(mb.fetch(rc.p, 16, h));
-    memcpy(pd->root, h, 32);
-    memcpy(pd->commit, h + 8, 32);
-    memcpy(h_commit, pd->commit, 32);
+    SP1HIP_TRY(basefold_data_fetch_commit(pd.get(), rc.u32(), h_commit, s));
     *out = pd.release();
     return SP1HIP_SUCCESS;
 }
@@ -587,41 +655,16 @@ int sp1hip_basefold_data_tree(const sp1hip_basefold_data_t* data, const uint32_t
 }
 
 size_t sp1hip_basefold_proof_size(int dim, const uint32_t* round_widths, int n_rounds, sp1hip_fri_config_t config) {
-    std::vector<uint32_t> w(round_widths, round_widths + n_rounds);
-    return proof_size(dim, w, config);
+    return basefold_proof_size(32, dim, round_widths, n_rounds, config);
 }
 
 int sp1hip_basefold_prove(const sp1hip_ext_t* h_point, int dim, sp1hip_basefold_data_t* const* rounds, int n_rounds,
                           const sp1hip_ext_t* h_claims, size_t n_claims, sp1hip_fri_config_t config,
                           sp1hip_challenger_t* challenger, uint8_t* h_proof, size_t* proof_len, sp1hip_stream_t stream) {
-    SP1HIP_REQUIRE(h_point && rounds && n_rounds > 0 && h_claims && challenger && proof_len, "null argument");
-    SP1HIP_REQUIRE(dim >= 1 && dim <= kb::TWO_ADICITY, "dim out of range");
-    SP1HIP_REQUIRE(config.num_queries > 0 && config.log_blowup >= 0 && config.proof_of_work_bits >= 0, "bad config");
-    std::vector<uint32_t> widths;
-    for (int r = 0; r < n_rounds; r++) {
-        SP1HIP_REQUIRE(rounds[r], "null round");
-        widths.push_back(rounds[r]->total_width);
-        if (rounds[r]->tree.s != S(stream)) rounds[r]->foreign_use = true;
-    }
-    const size_t need = proof_size(dim, widths, config);
-    if (!h_proof || *proof_len < need) {
-        *proof_len = need;
-        set_error("sp1hip_basefold_prove: proof buffer too small, need %zu bytes", need);
-        return SP1HIP_ERROR_BUFFER_TOO_SMALL;
-    }
-    std::vector<kb::Ext> point(dim);
-    memcpy(point.data(), h_point, (size_t)dim * 16);
-    DuplexChallenger ch = challenger->ch;  // commit to the transcript only on success
-    size_t written = 0;
-    SP1HIP_TRY(prove_trusted_mle_evaluations(point, rounds, n_rounds, reinterpret_cast<const kb::Ext*>(h_claims), n_claims,
-                                             config, ch, h_proof, need, &written, S(stream)));      // written in place
-    if (written != need) {
-        set_error("internal error: proof size %zu != expected %zu", written, need);
-        return SP1HIP_ERROR_RUNTIME;
-    }
-    *proof_len = written;
-    challenger->ch = ch;
-    return SP1HIP_SUCCESS;
+    SP1HIP_REQUIRE(rounds && n_rounds > 0 && challenger, "null argument");
+    std::vector<BasefoldData*> data(rounds, rounds + n_rounds);
+    InnerBasefoldBackend be(challenger->ch);
+    return basefold_prove_with(be, h_point, dim, data.data(), n_rounds, h_claims, n_claims, config, h_proof, proof_len, stream);
 }
 
 }  // extern "C"

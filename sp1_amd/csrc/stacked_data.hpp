@@ -25,7 +25,7 @@ struct StackedCore {
     int max_log_row_count = 0;
     std::vector<uint64_t> row_counts, column_counts;   // per table, the two padding tables appended
     uint64_t padding_column_count = 0;
-    std::atomic<bool> foreign_use{false};            // read on a stream other than `stream` (see sp1hip_basefold_data_s)
+    std::atomic<bool> foreign_use{false};            // read on a stream other than `stream` (see BasefoldData, basefold_host.hpp)
     ~StackedCore() { arena_free(d_dense, padded * 4, stream); }      // (after the derived handle released its BaseFold data)
 };
 

@@ -104,8 +104,8 @@ KB_HD Ext ext_mul_base(const Ext& a, uint32_t b) {
     return Ext{{mul(a.c[0], b), mul(a.c[1], b), mul(a.c[2], b), mul(a.c[3], b)}};
 }
 
-// x < 2^64 - 2^58 (any sum of four products of reduced words: 4 (p - 1)^2 = 2^64 - 2^58 + 2^50)  ->  x * 2^-32 mod p, fully
-// reduced. The high word is < 2^32 - 2^26 + 2^18 < 2p, so one conditional subtraction brings x under 2^32 p, where the
+// x <= 4 (p - 1)^2 = 2^64 - 2^58 + 2^50 (any sum of four products of reduced words)  ->  x * 2^-32 mod p, fully
+// reduced. The high word is <= 2^32 - 2^26 + 2^18 < 2p, so one conditional subtraction brings x under 2^32 p, where the
 // additive reduction applies: 6 VALU instructions (sub, min, mul_lo, mad_u64, sub, min) for FOUR products instead of two
 // reductions of two products and a modular add (11).
 KB_HD uint32_t monty_reduce_wide(uint64_t x) {

@@ -8,7 +8,7 @@ from sp1_amd.air import InteractionProgram, VCol
 P = 0x7F000001
 
 
-def make_gkr_chips(n_tuples, seed, with_empty=False, dup=2):
+def make_gkr_chips(n_tuples, seed, with_empty=False, dup=2, source=None):
     """Returns [(InteractionProgram, main [rows][w] Montgomery row-major, prep or None)] in name order.
 
     * "Alpha"  (main a, b, m):         sends   kind 5 (a, 2a + 3b + 7) with multiplicity m
@@ -16,8 +16,9 @@ def make_gkr_chips(n_tuples, seed, with_empty=False, dup=2):
                                        sends   kind 7 (s) with multiplicity 1
     * "Gamma"  (main s, one):          receives kind 7 (s) with multiplicity `one` (a column of ones)
     * "Omega"  zero rows, one send (only when with_empty)
-    Alpha lists every tuple `dup` times with multiplicity 1; Beta lists it once with multiplicity dup."""
-    rng = np.random.default_rng(seed)
+    Alpha lists every tuple `dup` times with multiplicity 1; Beta lists it once with multiplicity dup.
+    `source`: what the free columns are drawn from in place of default_rng(seed) (tests/kb_edges.py: EdgeSource)."""
+    rng = np.random.default_rng(seed) if source is None else source
     a = rng.integers(0, P, n_tuples, dtype=np.uint64)
     b = rng.integers(0, P, n_tuples, dtype=np.uint64)
     s = rng.integers(0, P, n_tuples, dtype=np.uint64)
@@ -45,3 +46,21 @@ def make_gkr_chips(n_tuples, seed, with_empty=False, dup=2):
         omega.send(9, [VCol.main(0), VCol.main(1), VCol.const(3)], VCol.main(1))
         chips.append((omega, np.zeros((0, 2), np.uint32), None))
     return chips
+
+
+def make_gkr_wide_chips(n_rows, n_values, seed, source=None):
+    """Two chips whose one interaction carries `n_values` values (the chips above carry at most three): "Sigma" sends kind 11
+    (its main columns 0 .. n_values - 1, the last one doubled plus 5) with multiplicity 1 (a column of ones), "Tau" lists the
+    same rows in another order and receives them. first_layers_kernel reduces its unreduced sums after every fourth value and
+    after the last one: n_values = 9 runs two full flushes and a tail of one, n_values = 8 two full flushes and no tail."""
+    rng = np.random.default_rng(seed) if source is None else source
+    vals = rng.integers(0, P, (n_rows, n_values), dtype=np.uint64)
+    ones = np.ones((n_rows, 1), np.uint64)
+    values = lambda: [VCol.main(k) for k in range(n_values - 1)] + [VCol.main(n_values - 1, 2) + 5]
+    sigma = InteractionProgram("Sigma", n_values + 1)
+    sigma.send(11, values(), VCol.main(n_values))
+    tau = InteractionProgram("Tau", n_values + 1)
+    tau.receive(11, values(), VCol.main(n_values))
+    sigma_main = np.concatenate([vals, ones], axis=1).astype(np.uint32)
+    tau_main = sigma_main[rng.permutation(n_rows)]
+    return [(sigma, orc.to_monty(sigma_main), None), (tau, orc.to_monty(tau_main), None)]

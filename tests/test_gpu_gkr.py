@@ -8,7 +8,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import pyoracle as orc  # noqa: E402
-from gkr_chips import make_gkr_chips  # noqa: E402
+from gkr_chips import make_gkr_chips, make_gkr_wide_chips  # noqa: E402
+from kb_edges import EdgeSource  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -53,6 +54,34 @@ def test_gkr_proof_matches_oracle(api, n_tuples, L, with_empty, dup):
     assert orc.gkr_verify(chips, [c[1].shape[0] for c in chips], L, got, v_ch) == 0
     point, opened = api.parse_logup_gkr_proof(got)
     assert point.shape == (L, 4) and [o[0] for o in opened] == [c[0].name for c in chips]
+
+
+@pytest.mark.parametrize("fused", ["1", "0"])
+@pytest.mark.parametrize("n_tuples,dup,wide_rows,n_values,L", [
+    (37, 3, 37, 9, 7),         # heights 111 / 37 / 37: not multiples of four (the scalar loads, partial quads); 9 values per
+                               # interaction: first_layers_kernel flushes at pending == 4 twice, then the tail of one
+    (64, 2, 100, 8, 8),        # heights 128 / 64 / 100: multiples of four (the vector loads); 8 values: two full flushes, no tail
+    (300, 3, 1024, 13, 10),    # multi-tile rows; three full flushes and a tail
+])
+def test_gkr_proof_of_edge_tables_matches_oracle(api, monkeypatch, n_tuples, dup, wide_rows, n_values, L, fused):
+    """The chips of make_gkr_chips and two chips with wide interactions, their free columns drawn from the stored-domain edge
+    pool (tests/kb_edges.py): whole columns of p - 1 or 0x7effffff under the unreduced sums of first_layers_kernel
+    (four products of a challenge word and a value per 64-bit accumulator, kb::monty_reduce_wide) and of the opening kernel
+    (kb::dot_add). fused = 0: the level-by-level tree (first_layer_kernel)."""
+    monkeypatch.setenv("SP1HIP_GKR_FUSED", fused)
+    src = EdgeSource(700 + L)
+    chips = make_gkr_chips(n_tuples, 10 + L, True, dup, source=src) + make_gkr_wide_chips(wide_rows, n_values, 10 + L, source=src)
+    assert [c[0].name for c in chips] == sorted(c[0].name for c in chips)
+    o_ch, g_ch = orc.Challenger(), api.DuplexChallenger()
+    seed = orc.random_felts((9,), L)
+    o_ch.observe(seed)
+    g_ch.observe(seed)
+    v_ch = o_ch.clone()
+    want = orc.gkr_prove(chips, L, o_ch)
+    got = api.logup_gkr(_dev(api, chips), L, g_ch)
+    assert got == want
+    assert np.array_equal(g_ch.state(), o_ch.state())
+    assert orc.gkr_verify(chips, [c[1].shape[0] for c in chips], L, got, v_ch) == 0
 
 
 @pytest.mark.parametrize("flat_slots", ["0", "64", "1024"])     # 0: every pass one workgroup per tile; 64 / 1024: both forms inside one layer

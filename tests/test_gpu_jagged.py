@@ -8,6 +8,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import pyoracle as orc  # noqa: E402
+from kb_edges import EdgeSource  # noqa: E402
 from test_oracle_jagged import CASES, claims_for, make_rounds  # noqa: E402
 
 
@@ -31,10 +32,10 @@ BIG = [
 
 @pytest.mark.parametrize("factored", ["1", "0"])
 @pytest.mark.parametrize("shapes,L,lsh,batch", CASES + BIG)
-def test_jagged_proof_matches_oracle(api, monkeypatch, shapes, L, lsh, batch, factored):
+def test_jagged_proof_matches_oracle(api, monkeypatch, shapes, L, lsh, batch, factored, source=None):
     monkeypatch.setenv("SP1HIP_JAGGED_FACTORED", factored)       # "0": always materialise the j tables
     lb, nq, pw = 1, 6, 4
-    rounds, tabs = make_rounds(shapes, L, lsh, batch, 7 + L, lb)
+    rounds, tabs = make_rounds(shapes, L, lsh, batch, 7 + L, lb, source)
     jp = api.JaggedProver(L, lsh, batch, lb)
     g_rounds, g_commits = [], []
     for tb in tabs:
@@ -68,6 +69,32 @@ def test_jagged_two_pass_form_of_rounds_0_and_1_gives_the_same_bytes(api, monkey
     SP1HIP_JAGGED_LOOKAHEAD=0 keeps the two-pass form."""
     monkeypatch.setenv("SP1HIP_JAGGED_LOOKAHEAD", "0")
     test_jagged_proof_matches_oracle(api, monkeypatch, shapes, L, lsh, batch, "1")
+
+
+# Which kernel of jagged.hip proves the first rounds is decided by the heights (sp1hip_jagged_prove: g = the OR of every
+# column's start in the dense order, i.e. of the table heights' multiples):
+#   odd heights            g & 1: the generic segment kernels (jg_round0_sum, jg_fold0_sum)
+#   heights = 2 mod 4      J stays factored: jg_round0_tables, then the generic jg_fold0_sum<false>
+#   heights = 4 mod 8      tables_mult4: jg_round0_tables, then jg_fold_tables<1, true>
+#   heights = 0 mod 8      skip_level1: jg_round01_tables (rounds 0 and 1 in one pass), then jg_fold_tables<2, true>;
+#                          with SP1HIP_JAGGED_LOOKAHEAD=0: jg_round0_tables, jg_fold_tables<1, false>, jg_fold_tables<2, true>
+EDGE = [
+    ("odd", [[(1 << 10, 3), (777, 5), (0, 2), (33, 7)]], 10, 6, 4, "1"),
+    ("2mod4", [[(1 << 10, 3), (770, 5), (6, 7)]], 10, 6, 4, "1"),
+    ("4mod8", [[(1 << 10, 3), (772, 5), (12, 7)]], 10, 6, 4, "1"),
+    ("0mod8", [[(1 << 10, 3), (768, 5), (0, 2), (64, 7)], [(1 << 12, 9), (4032, 2), (128, 1), (2048, 30)]], 12, 8, 4, "1"),
+    ("0mod8-two-pass", [[(1 << 10, 3), (768, 5), (0, 2), (64, 7)], [(1 << 12, 9), (4032, 2), (128, 1), (2048, 30)]], 12, 8, 4, "0"),
+]
+
+
+@pytest.mark.parametrize("factored", ["1", "0"])
+@pytest.mark.parametrize("case,shapes,L,lsh,batch,lookahead", EDGE, ids=[e[0] for e in EDGE])
+def test_jagged_proof_of_edge_tables_matches_oracle(api, monkeypatch, case, shapes, L, lsh, batch, lookahead, factored):
+    """Tables of stored-domain edge words (tests/kb_edges.py: whole columns of p - 1 or 0x7effffff, 0 / p - 1 alternating,
+    pool words per row) through every form of the first rounds, see the list above: the unreduced dot_add / edot_add sums
+    of jg_round0_tables, jg_round01_tables and jg_fold_tables see the largest 16-bit halves in every term of a column."""
+    monkeypatch.setenv("SP1HIP_JAGGED_LOOKAHEAD", lookahead)
+    test_jagged_proof_matches_oracle(api, monkeypatch, shapes, L, lsh, batch, factored, EdgeSource(500 + L))
 
 
 def test_jagged_prove_rejects_bad_input_and_keeps_transcript(api):

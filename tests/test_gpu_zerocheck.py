@@ -8,6 +8,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import pyoracle as orc  # noqa: E402
+from kb_edges import EdgeSource  # noqa: E402
 from test_oracle_zerocheck import setup  # noqa: E402
 
 
@@ -49,6 +50,29 @@ def test_zerocheck_matches_oracle(api, heights, L):
     want = orc.zerocheck_prove(zc, L, zeta, alpha, gkr, publics, o_ch)
     openings = np.concatenate([c.openings for c in zc])
     got = api.zerocheck(_gpu_chips(api, chips), L, zeta, openings, alpha, gkr, publics, g_ch)
+    assert got == want
+    assert np.array_equal(g_ch.state(), o_ch.state())
+    assert orc.zerocheck_verify(zc, [c.real_rows for c in zc], L, zeta, alpha, gkr, publics, got, v_ch) == 0
+
+
+@pytest.mark.parametrize("heights,L", [
+    ({"Mul": 5, "Affine": 3, "Sbox": 6}, 3),
+    ({"Affine": 7, "Empty": 0, "Sbox": 2}, 4),
+    ({"Affine": 1000, "Mul": 4096, "Sbox": 2049, "Sbox2": 1}, 12),
+    ({"Chain": 300, "Manyregs": 1000, "Mul": 77}, 10),
+])
+def test_zerocheck_of_edge_traces_matches_oracle(api, heights, L):
+    """The same AIRs over traces whose free columns come from the stored-domain edge pool (tests/kb_edges.py): whole columns of
+    p - 1 or 0x7effffff, 0 / p - 1 alternating, pool words per row; the dependent columns are computed, so every
+    constraint still holds."""
+    chips, zc, zeta, alpha, gkr, publics, o_ch = setup(heights, L, 40 + L, EdgeSource(300 + L))
+    g_ch = api.DuplexChallenger()
+    g_ch.observe(orc.random_felts((8,), 40 + L))
+    assert np.array_equal(g_ch.sample_point(L), zeta)
+    assert np.array_equal(g_ch.sample_ext_element(), alpha) and np.array_equal(g_ch.sample_ext_element(), gkr)
+    v_ch = o_ch.clone()
+    want = orc.zerocheck_prove(zc, L, zeta, alpha, gkr, publics, o_ch)
+    got = api.zerocheck(_gpu_chips(api, chips), L, zeta, np.concatenate([c.openings for c in zc]), alpha, gkr, publics, g_ch)
     assert got == want
     assert np.array_equal(g_ch.state(), o_ch.state())
     assert orc.zerocheck_verify(zc, [c.real_rows for c in zc], L, zeta, alpha, gkr, publics, got, v_ch) == 0

@@ -10,11 +10,13 @@ import pyoracle as orc
 P = 0x7F000001
 
 
-def make_rounds(shapes_per_round, L, lsh, batch, seed, lb=1):
+def make_rounds(shapes_per_round, L, lsh, batch, seed, lb=1, source=None):
+    """`source`: where the table words come from in place of orc.random_felts (tests/kb_edges.py: EdgeSource)."""
     rounds, tables_per_round = [], []
     for r, shapes in enumerate(shapes_per_round):
-        tabs = [orc.random_felts((h, w), seed + 100 * r + k) if h else np.zeros((0, w), np.uint32)
-                for k, (h, w) in enumerate(shapes)]
+        draw = (lambda h, w, k: orc.random_felts((h, w), seed + 100 * r + k)) if source is None else \
+            (lambda h, w, k: orc.to_monty(source.integers(0, P, (h, w), dtype=np.uint64).astype(np.uint32)))
+        tabs = [draw(h, w, k) if h else np.zeros((0, w), np.uint32) for k, (h, w) in enumerate(shapes)]
         tables_per_round.append(tabs)
         rounds.append(orc.JaggedRound(tabs, L, lsh, batch, lb))
     return rounds, tables_per_round

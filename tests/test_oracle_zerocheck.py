@@ -13,10 +13,10 @@ P = 0x7F000001
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "kb_shrink_basefold.npz"))
 
 
-def setup(heights, L, seed):
+def setup(heights, L, seed, source=None):
     pv = np.array([77, 12345], np.uint32)
     publics = orc.to_monty(pv)
-    chips = make_chips(heights, seed, pv)
+    chips = make_chips(heights, seed, pv, source)
     ch = orc.Challenger()
     ch.observe(orc.random_felts((8,), seed))
     zeta = ch.sample_point(L)

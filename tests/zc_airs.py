@@ -106,11 +106,12 @@ def trace_manyregs(rows, rng, n=48):
     return np.stack([a, b, c, ab], axis=1).astype(np.uint32)
 
 
-def make_chips(heights, seed, pv):
+def make_chips(heights, seed, pv, source=None):
     """heights: dict name -> real rows; the name's prefix picks the AIR ('Affine*', 'Sbox*', anything else =
     Mul). Returns [(name, AirProgram, main, prep)] in BTreeMap (name) order like the reference, traces in
-    Montgomery form, row-major, real rows only."""
-    rng = np.random.default_rng(seed)
+    Montgomery form, row-major, real rows only. `source`: what the trace_* functions draw their free columns from in place of
+    default_rng(seed) (tests/kb_edges.py: EdgeSource); the dependent columns are computed from them either way."""
+    rng = np.random.default_rng(seed) if source is None else source
     out = []
     for name in sorted(heights):
         h = heights[name]

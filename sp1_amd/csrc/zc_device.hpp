@@ -1,5 +1,5 @@
 // sp1_amd/csrc/zc_device.hpp — device-side pieces of the zerocheck round shared by the bytecode interpreter
-// (zerocheck.hip) and the per-chip COMPILED constraint kernels (zc_codegen.cpp generates their source against this
+// (zc_kernels.hpp, launched by zerocheck.hip) and the per-chip COMPILED constraint kernels (zc_codegen.cpp generates their source against this
 // header; hipcc at build time or hipRTC at run time compiles it). See zerocheck.hip for the reference citations.
 #pragma once
 #include "kb31.hpp"
@@ -8,6 +8,32 @@ namespace sp1hip {
 
 enum ZcOp : uint32_t { ZC_LOAD_MAIN = 0, ZC_LOAD_PREP = 1, ZC_CONST = 2, ZC_PUBLIC = 3, ZC_ADD = 4, ZC_SUB = 5, ZC_MUL = 6,
                        ZC_NEG = 7, ZC_ASSERT_ZERO = 8 };
+
+// ---- the interpreter's instruction words [op | flags, dst, a, b]: written by the host compiler (zc_compile.cpp), read by the
+// kernels (zc_kernels.hpp)
+constexpr uint32_t ZC_GKR_FLAG = 0x100u;   // bits 8..11: column j of this load is the first load of that column (host)
+constexpr uint32_t ZC_A_PREV = 0x1000u, ZC_B_PREV = 0x2000u;   // operand = the value the previous instruction produced
+constexpr uint32_t ZC_DST_TEMP = 0x4000u;  // the result is only forwarded, never stored in the register file
+                                           // bits 16..17: (number of consecutive columns of a LOAD) - 1
+constexpr uint32_t ZC_TOUCH = 9;           // pseudo-op: column never loaded by the constraints (GKR term only)
+// internal forms with an immediate operand (host peephole `fold_immediates`: an ADD / SUB / MUL one of whose operands is
+// a CONST): the constant travels in the instruction word — no register, no LDS access, and in the extension rounds a
+// constant factor is 4 base products instead of a full 16-product extension multiply
+constexpr uint32_t ZC_ADDC = 10, ZC_SUBC = 11, ZC_CSUB = 12, ZC_MULC = 13;
+// fused multiply-add by a constant (register allocation, host): acc + term * c for a MULC whose only use is the ADD / SUB
+// (as subtrahend, c negated) that follows it — the linear combinations real chips are full of (limb recompositions, the
+// closed-form Poseidon2 rounds) become ONE dispatch per term, and the running sum is forwarded from instruction to
+// instruction in VGPRs instead of going through the register file. Word: op | flags, dst | (acc register << 16), term
+// register, c; ZC_A_PREV: term = previous value, ZC_B_PREV: acc = previous value.
+constexpr uint32_t ZC_MADC = 14;
+constexpr uint32_t ZC_RSUB = 15;           // b - a: a SUB whose forwarded operand is the subtrahend (register allocation, host)
+// acc + a * b / acc - a * b: a MUL whose single use is the ADD / SUB that is the next value-producing instruction (host peephole in
+// allocate_registers, like MADC). The sums of products real chips are made of (MulOperation: 136 byte products in 16 chains) are
+// emitted term by term with the running sum as the previous value, so a chain becomes MUL, MAD, MAD, ... with the sum FORWARDED:
+// two LDS reads per term and no write, instead of a MUL (two reads) and an ADD (a read and a write) — and half the decodes.
+// Word: op | flags, dst | (acc register << 16), a, b; ZC_B_PREV: acc = previous value (a, b from the file); else ZC_A_PREV: a =
+// previous value.
+constexpr uint32_t ZC_MAD = 16, ZC_MSB = 17;
 
 // One chip of the current round (device array; every field is wave-uniform in the kernels).
 struct ZcDesc {

@@ -6,7 +6,7 @@
 // per CU): 114 ms of round kernels per shard proof against 16 ms for a whole core shard (profiles/r05_precompile_before.txt).
 // The constraints are a handful of REGULAR loop nests over (x, y, z), so a caller's program may carry `[16, 5, base_col]` in front of
 // the 2,858 asserts that follow `assert_bool(is_real)`; the planner checks the hint against the SSA on a pseudo-random row
-// (zerocheck.hip) and the asserts are then evaluated by eleven self-contained pieces with a dozen live values each:
+// (zc_compile.cpp) and the asserts are then evaluated by eleven self-contained pieces with a dozen live values each:
 //   q = 0          step flags (24 booleans, their sum, the round index), the bits of A''[0, 0] and the round-constant xor;
 //                  also carries the GKR term of the two column groups no constraint reads (export, preimage)
 //   q = 1 + x      lane column x: C'[x, z] = xor3(C[x, z], C[x - 1, z], C[x + 1, z - 1]), the parity check of A'[., x, z] against

@@ -8,7 +8,7 @@
 // ~3,800 instruction words per row pair and node whose operands make a round trip through the LDS register file each, with one
 // scalar instruction of decode per vector instruction: 21 % of the VALU issue rate and 0.9 TB/s on the real-chip shard
 // (profiles/r04_traffic.json). A caller's program may therefore carry a HINT pseudo-instruction (op 16: kind, first main
-// column) in front of those constraints; the planner (zerocheck.hip) then drops the 163 asserts from the bytecode and emits
+// column) in front of those constraints; the planner (zc_compile.cpp) then drops the 163 asserts from the bytecode and emits
 // nine self-contained pieces instead — external round q (q = 0..7) and the 20 internal rounds (q = 8) — evaluated here with the
 // state in VGPRs: the sequential form of the reference, no register file, no decode. The hint changes nothing but speed: the
 // SSA program stays the definition (the oracle and the verifier ignore op 16), the planner CHECKS the hint against the SSA

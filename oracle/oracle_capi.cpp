@@ -612,6 +612,20 @@ void orc_bb_commit_mles(const uint32_t* const* mles, const int* widths, int n_ml
     for (int i = 0; i < 8; i++) commit[i] = c.d[i].v;
     if (tree_out) memcpy(tree_out, tree.data(), tree.size() * sizeof(orcbb::Digest));
 }
+// tensors [h][w_k] row-major of any content (not codewords) -> tree[2 h - 1][8] leaf-first, commitment[8]
+void orc_bb_merkle_commit(const uint32_t* const* tensors, const int* widths, int n_tensors, size_t h, uint32_t* tree_out, uint32_t* commit) {
+    std::vector<const orcbb::F*> ptrs;
+    for (int k = 0; k < n_tensors; k++) ptrs.push_back(reinterpret_cast<const orcbb::F*>(tensors[k]));
+    std::vector<int> ws(widths, widths + n_tensors);
+    std::vector<orcbb::Digest> tree;
+    orcbb::Digest c;
+    orcbb::merkle_commit(ptrs, ws, h, &tree, &c);
+    for (int i = 0; i < 8; i++) commit[i] = c.d[i].v;
+    memcpy(tree_out, tree.data(), tree.size() * sizeof(orcbb::Digest));
+}
+void orc_bb_rs_encode(const uint32_t* in, int log_n, int w, int log_blowup, uint32_t* out) {
+    orcbb::rs_encode(reinterpret_cast<const orcbb::F*>(in), log_n, w, log_blowup, reinterpret_cast<orcbb::F*>(out));
+}
 void orc_bb_permute(uint32_t* states, size_t n) {
     for (size_t i = 0; i < n; i++) orcbb::permute(reinterpret_cast<orcbb::F*>(states + 16 * i));
 }

@@ -166,6 +166,29 @@ def bb_commit_mles(mles, log_blowup, want_codewords=False, want_tree=False):
     return commit, cws, tree
 
 
+def bb_rs_encode(m, log_blowup):
+    """[n][w] row-major -> [n << log_blowup][w], rows bit-reversed (bb_commit.hpp rs_encode)."""
+    m = _arr(m)
+    log_n = m.shape[0].bit_length() - 1
+    out = np.zeros((m.shape[0] << log_blowup, m.shape[1]), np.uint32)
+    L = lib()
+    L.orc_bb_rs_encode.restype = None
+    L.orc_bb_rs_encode(_p(m), log_n, m.shape[1], log_blowup, _p(out))
+    return out
+
+
+def bb_merkle_commit(tensors):
+    """Row-major tensors [h][w_k] of any content -> (tree [2 h - 1][8] leaf-first, root [8], commitment [8])."""
+    tensors = [_arr(t) for t in tensors]
+    h = tensors[0].shape[0]
+    widths = (C.c_int * len(tensors))(*[t.shape[1] for t in tensors])
+    tree, commit = np.zeros((2 * h - 1, 8), np.uint32), np.zeros(8, np.uint32)
+    L = lib()
+    L.orc_bb_merkle_commit.restype = None
+    L.orc_bb_merkle_commit(_ptr_array(tensors), widths, len(tensors), C.c_size_t(h), _p(tree), _p(commit))
+    return tree, tree[-1].copy(), commit
+
+
 def bb_permute(states):
     s = np.ascontiguousarray(states, dtype=np.uint32).copy()
     L = lib()

@@ -640,6 +640,27 @@ def bb_commit_mles(mles, log_blowup, stream=None):
     return commit, [ColMajor(c, N, m.width) for c, m in zip(cws, mles)], tree
 
 
+def bb_rs_encode_batch(mle, log_blowup, stream=None):
+    """BabyBear RS encode of one ColMajor tensor (sp1hip_bb_rs_encode_batch): every column's 2^lg_n coefficients -> its
+    2^(lg_n + log_blowup) evaluations in bit-reversed row order, as a new ColMajor."""
+    lg_n = mle.height.bit_length() - 1
+    N = mle.height << log_blowup
+    out = device_words(N * mle.width)
+    check(_L().sp1hip_bb_rs_encode_batch(_dptr(out), _dptr(mle.words), lg_n, log_blowup, mle.width, _stream_ptr(stream)))
+    return ColMajor(out, N, mle.width)
+
+
+def bb_merkle_commit(tensors, stream=None):
+    """BabyBear `commit_tensors` (sp1hip_bb_merkle_commit) over ColMajor tensors of equal power-of-two height, of any content.
+    Returns (commitment [8] numpy, root [8] numpy, tree words as a device tensor [(2 h - 1) * 8], layers leaf-first)."""
+    h = tensors[0].height
+    tree = device_words((2 * h - 1) * 8)
+    rc = device_words(16)
+    check(_L().sp1hip_bb_merkle_commit(_tensor_array(tensors), len(tensors), h.bit_length() - 1, _dptr(tree), _dptr(rc), _stream_ptr(stream)))
+    rc = to_host(rc)
+    return rc[8:].copy(), rc[:8].copy(), tree
+
+
 def bb_poseidon2_permute(states, stream=None):
     """[n, 16] numpy BabyBear Montgomery words -> permuted (sp1hip_bb_poseidon2_permute)."""
     d = to_device(np.ascontiguousarray(states, dtype=np.uint32).reshape(-1))

@@ -19,102 +19,13 @@
 #include <unordered_map>
 #include <vector>
 
+#include "bb31.hpp"
 #include "common.hpp"
 #include "device_ctx.hpp"
 #include "tensor_table.hpp"
 
 namespace sp1hip {
 namespace bb {
-
-constexpr uint32_t P = 0x78000001u;
-constexpr uint32_t MU = 0x88000001u;             // p^-1 mod 2^32  (p MU = 1 mod 2^32)
-constexpr int TWO_ADICITY = 27;
-static_assert((uint32_t)(P * MU) == 1u, "Montgomery constant");
-
-__host__ __device__ __forceinline__ uint32_t monty_reduce(uint64_t x) {       // x < 2^32 p  ->  x 2^-32 mod p
-    const uint32_t t = (uint32_t)x * MU;
-    const uint64_t u = (uint64_t)t * P;
-    const uint32_t hi = (uint32_t)((x - u) >> 32);
-    return x < u ? hi + P : hi;
-}
-__host__ __device__ __forceinline__ uint32_t add(uint32_t a, uint32_t b) { const uint32_t s = a + b; return s >= P ? s - P : s; }
-__host__ __device__ __forceinline__ uint32_t sub(uint32_t a, uint32_t b) { return a >= b ? a - b : a + P - b; }
-__host__ __device__ __forceinline__ uint32_t mul(uint32_t a, uint32_t b) { return monty_reduce((uint64_t)a * b); }
-inline uint32_t to_monty(uint32_t c) {
-    const uint64_t r = ((uint64_t)1 << 32) % P;
-    return monty_reduce((uint64_t)(c % P) * (uint32_t)((r * r) % P));
-}
-inline uint32_t pow(uint32_t b, uint64_t e) { uint32_t r = to_monty(1); while (e) { if (e & 1) r = mul(r, b); b = mul(b, b); e >>= 1; } return r; }
-inline uint32_t two_adic_generator(int bits) {
-    uint32_t g = pow(to_monty(31), (P - 1) >> TWO_ADICITY);
-    for (int i = bits; i < TWO_ADICITY; i++) g = mul(g, g);
-    return g;
-}
-
-struct RoundConstants { uint32_t ext[8][16], internal[13]; };
-static const uint32_t RC_CANONICAL[30][16] = {
-#include "bb_poseidon2_rc.inc"
-};
-inline RoundConstants make_round_constants() {
-    RoundConstants rc;
-    for (int r = 0; r < 4; r++)
-        for (int i = 0; i < 16; i++) { rc.ext[r][i] = to_monty(RC_CANONICAL[r][i]); rc.ext[4 + r][i] = to_monty(RC_CANONICAL[17 + r][i]); }
-    for (int r = 0; r < 13; r++) rc.internal[r] = to_monty(RC_CANONICAL[4 + r][0]);
-    return rc;
-}
-
-__device__ __forceinline__ void external_linear(uint32_t* s) {
-#pragma unroll
-    for (int j = 0; j < 16; j += 4) {
-        const uint32_t x0 = s[j], x1 = s[j + 1], x2 = s[j + 2], x3 = s[j + 3];
-        const uint32_t t01 = add(x0, x1), t23 = add(x2, x3), t0123 = add(t01, t23);
-        const uint32_t t01123 = add(t0123, x1), t01233 = add(t0123, x3);
-        s[j] = add(t01123, t01);
-        s[j + 1] = add(t01123, add(x2, x2));
-        s[j + 2] = add(t01233, t23);
-        s[j + 3] = add(t01233, add(x0, x0));
-    }
-    uint32_t sums[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) sums[k] = add(add(s[k], s[k + 4]), add(s[k + 8], s[k + 12]));
-#pragma unroll
-    for (int j = 0; j < 16; j++) s[j] = add(s[j], sums[j & 3]);
-}
-// s_i <- (sum + d_i s_i) 2^-32, d = [-2, 1, 2, 4, ..., 2^13, 2^15]: one 64-bit sum, one shift-add and one reduction per lane
-__device__ __forceinline__ void internal_linear(uint32_t* s) {
-    uint64_t sum = 0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) sum += s[i];
-    const uint64_t v0 = s[0], neg0 = v0 ? P - v0 : 0;
-    const uint32_t n0 = monty_reduce(sum - v0 + neg0);
-#pragma unroll
-    for (int i = 1; i < 16; i++) s[i] = monty_reduce(sum + ((uint64_t)s[i] << (i == 15 ? 15 : i - 1)));
-    s[0] = n0;
-}
-__device__ __forceinline__ uint32_t sbox(uint32_t x) {
-    const uint32_t x2 = mul(x, x), x3 = mul(x2, x), x4 = mul(x2, x2);
-    return mul(x4, x3);
-}
-__device__ __forceinline__ void permute(uint32_t* s, const RoundConstants* __restrict__ rc) {
-    external_linear(s);
-#pragma unroll 1
-    for (int r = 0; r < 4; r++) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) s[i] = sbox(add(s[i], rc->ext[r][i]));
-        external_linear(s);
-    }
-#pragma unroll 1
-    for (int r = 0; r < 13; r++) {
-        s[0] = sbox(add(s[0], rc->internal[r]));
-        internal_linear(s);
-    }
-#pragma unroll 1
-    for (int r = 4; r < 8; r++) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) s[i] = sbox(add(s[i], rc->ext[r][i]));
-        external_linear(s);
-    }
-}
 
 __global__ __launch_bounds__(256) void bb_permute_kernel(uint32_t* __restrict__ states, size_t n, const RoundConstants* __restrict__ rc) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

@@ -106,6 +106,9 @@ def main():
     ap.add_argument("--in-flight", type=int, default=0, help="after the shard-by-shard pass, prove ALL shards again through the library's "
                     "prover pool with this many proofs in flight (tables resident in HBM; proofs must equal the first pass's)")
     ap.add_argument("--only-kinds", default="", help="comma-separated shard kinds: build every shard, prove only these (a profile of one kind)")
+    ap.add_argument("--device-keccak", action="store_true", help="Keccak shards: make the KeccakPermute / KeccakPermuteControl tables on the "
+                    "device from the executor's event records (api.tracegen_riscv_keccak) instead of taking the tracer's; the shard's "
+                    "other chips stay as they are, and the proofs are the same bytes")
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--out", default="")
@@ -131,7 +134,8 @@ def main():
     shards, gevs, kept, cycles, last, resident, pvs, pk, pk_prep, warmed = [], [], {}, 0, None, [], [], None, None, {}
     t_all = time.perf_counter()
     t_prev = t_all
-    gen = X.program_shards(ex, shard_cycles, device=device, core_limit=args.core_shards or None)
+    keccak_events = [] if args.device_keccak and not args.dry_run else None
+    gen = X.program_shards(ex, shard_cycles, device=device, core_limit=args.core_shards or None, keccak_events=keccak_events)
     while True:
         try:
             kind, machine, tabs, publics, gev, sh = next(gen)
@@ -168,6 +172,12 @@ def main():
                 row["setup_ms"] = round(1e3 * (time.perf_counter() - t0), 2)
             assert sorted(a.name for a, _ in machine if tabs[a.name][0] is not None) == sorted(pk_prep), "a shard without the program's preprocessed chips"
             chips = [(a, i, to_col_major(tabs[a.name][1]), pk_prep.get(a.name)) for a, i in machine]
+            if keccak_events is not None and kind == "keccak":
+                from sp1_amd.machines import riscv_more_trace as MT
+                names = ("KeccakPermute", "KeccakPermuteControl")
+                made = dict(zip(names, MT.keccak_device_tables(keccak_events.pop(), [int(tabs[n][1].shape[0]) for n in names])))
+                chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
+                row["device_keccak"] = True
             tabs.clear()
             pv = RT.to_monty_np(publics)
             commit = pk.preprocessed_commit

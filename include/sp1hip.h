@@ -497,6 +497,25 @@ int sp1hip_tracegen_riscv_alu_width(int chip);       /* columns of the chip's ta
 int sp1hip_tracegen_riscv_alu(int chip, uint32_t* d_table, uint32_t height, const sp1hip_rv64_alu_event_t* d_events, uint32_t n_events,
                               sp1hip_stream_t stream);
 
+/* Device trace generation for the two chips of a KECCAK_PERMUTE precompile shard, from the executor's event records as they are
+ * (sp1hip_rv64_keccak_events below: n_events x 77 u64 on the device — [0] clk, [1] state pointer, [2 + 2i] / [3 + 2i] the previous
+ * timestamp and the word read of state word i < 25, [52 + i] the word written). The reference fills both tables on the host
+ * (crates/core/machine/src/syscall/precompiles/keccak256/trace.rs:L63-L162, controller.rs:L155-L237) and has no device filler
+ * for them; a call's rows are ~253 KB of table for a 616-byte event. Output as above: column-major [width][height] Montgomery words.
+ *   sp1hip_tracegen_riscv_keccak          KeccakPermute, width 2640: row 24 e + r is round r of event e — KeccakCols (step_flags[24],
+ *       export, preimage, a, c, c_prime, a_prime, a_prime_prime, a_prime_prime_0_0_bits, a_prime_prime_prime_0_0_limbs), clk_high,
+ *       clk_low, state_addr[3], index, is_real. The permutation is computed from the words read. A padding row q >= 24 n_events is
+ *       round q mod 24 of the permutation of the zero state with clk, state_addr, index and is_real zero. Needs 24 n_events <= height.
+ *   sp1hip_tracegen_riscv_keccak_control  KeccakPermuteControl, width 634: one row per event — clk_high, clk_low, SyscallAddrOperation,
+ *       25 AddrAddOperation values, is_real, 25 initial and 25 final MemoryAccessCols (reads at clk against the previous timestamps,
+ *       writes at clk + 1 against clk), final_value from the words written. Padding rows are zero. Needs n_events <= height.
+ * A null pointer is accepted only with a zero count / height; height == 0 succeeds without a launch. */
+int sp1hip_tracegen_riscv_keccak_width(void);            /* 2640 */
+int sp1hip_tracegen_riscv_keccak_control_width(void);    /* 634 */
+int sp1hip_tracegen_riscv_keccak(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_keccak_control(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events,
+                                         sp1hip_stream_t stream);
+
 /* ---------------------------------------------------------------- guest execution (host code, no device work)
  * An rv64im executor for SP1 guest ELFs: what `MinimalExecutor` + `TracingVM` do for the core prover
  * (/root/reference/crates/core/executor/src/minimal.rs, tracing.rs:L57-L147, vm.rs:L139-L431; the controller's shard loop is

@@ -571,6 +571,31 @@ def tracegen_riscv_alu(chip, events, height, stream=None):
     return ColMajor(out, int(height), width)
 
 
+KECCAK_EVENT_WORDS = 77                                                              # SP1HIP_RV64_KECCAK_WORDS
+
+
+def _tracegen_keccak(fn, events, height, stream):
+    width = getattr(_L(), fn + "_width")()
+    n = int(events.shape[0])
+    assert events.dtype == torch.int64 and (n == 0 or (events.is_cuda and events.shape[1] == KECCAK_EVENT_WORDS and events.is_contiguous()))
+    out = device_words(width * int(height))
+    check(getattr(_L(), fn)(_dptr(out), int(height), _dptr(events) if n else None, n, _stream_ptr(stream)))
+    return ColMajor(out, int(height), width)
+
+
+def tracegen_riscv_keccak(events, height, stream=None):
+    """`generate_trace_device` for the KeccakPermute chip (sp1hip_tracegen_riscv_keccak): events = a device int64 tensor [n, 77]
+    of the executor's KECCAK_PERMUTE records (riscv_exec.ExecutedShard.keccak); 24 rows per event, height >= 24 n. Returns the
+    column-major [2640][height] table as a ColMajor."""
+    return _tracegen_keccak("sp1hip_tracegen_riscv_keccak", events, height, stream)
+
+
+def tracegen_riscv_keccak_control(events, height, stream=None):
+    """The same events' KeccakPermuteControl table (sp1hip_tracegen_riscv_keccak_control): one row per event, height >= n;
+    column-major [634][height]."""
+    return _tracegen_keccak("sp1hip_tracegen_riscv_keccak_control", events, height, stream)
+
+
 class ProvingKey:
     """`ProvingKey` of the AirProver slot: the preprocessed commitment round + the verifying key (sp1hip_setup).
     Keeps the preprocessed device tables alive."""

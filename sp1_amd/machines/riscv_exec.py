@@ -439,7 +439,7 @@ def split_thresholds(program_rows):
     return out
 
 
-def program_shards(executor, max_cycles, device="cpu", core_limit=None):
+def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_events=None):
     """Every shard of a run, in the order the reference's controller emits them: the core shards as the program executes
     (`(kind, machine, tables, publics, global events, ExecutedShard)` with kind = "core"), then one precompile shard for the
     KECCAK_PERMUTE, POSEIDON2, SHA_EXTEND and SHA_COMPRESS calls each if there were any ("keccak", "poseidon2", "sha_extend",
@@ -490,6 +490,8 @@ def program_shards(executor, max_cycles, device="cpu", core_limit=None):
         kk = torch.as_tensor(kk, device=device)
         rd = kk[:, 2:52].reshape(-1, 25, 2)
         machine, tables, publics, gev = MT.precompile_shard_from(kk[:, 0], kk[:, 1], rd[:, :, 1].contiguous(), rd[:, :, 0].contiguous(), device, ctx=ctx)
+        if keccak_events is not None:
+            keccak_events.append(kk)
         yield "keccak", machine, tables, publics, gev, None
     for pp in chunks("poseidon2", poseidon2):
         pp = torch.as_tensor(pp, device=device)

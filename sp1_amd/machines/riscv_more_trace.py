@@ -174,6 +174,20 @@ def _mem_access_t(tb, prefix, prev_val, t_prev, t_cur):
     tb.set(prefix + ".diff_high_limb", d >> 16)
 
 
+def keccak_control_table(clk, addr, pre, t_prev, post, dev):
+    """KeccakPermuteControlChip::generate_trace_into (keccak256/controller.rs:L155-L237): one row per event — the reads of the 25
+    state words at clk, their writes (`post` [n, 25]) at clk + 1. Returns the table and the state pointer's limbs."""
+    ct = RT.Table(R.chip("KeccakPermuteControl")[0], int(clk.shape[0]), dev)
+    ct.set("clk_high", clk >> 24); ct.set("clk_low", clk & 0xFFFFFF); ct.set("is_real", 1)
+    al = _syscall_addr_t(ct, "state_addr", addr)
+    for i in range(25):
+        ct.set("addrs.%d.value" % i, _limbs_t(addr + 8 * i)[:, :3])
+        _mem_access_t(ct, "initial_memory_access.%d" % i, pre[:, i], t_prev[:, i], clk)
+        _mem_access_t(ct, "final_memory_access.%d" % i, pre[:, i], clk, clk + 1)
+        ct.set("final_value.%d" % i, _limbs_t(post[:, i]))
+    return ct, al
+
+
 def precompile_shard(n_events, seed=0, device="cpu", clk0=(5 << 24) + 1001):
     """A KECCAK_PERMUTE precompile shard of `n_events` random syscalls (see precompile_shard_from)."""
     dev = torch.device(device)
@@ -199,19 +213,24 @@ def precompile_shard_from(clk, addr, pre, t_prev, device="cpu", ctx=None):
     tr.dev, tr.tables = dev, {}
     kp, post = keccak_permute_table(clk, addr, pre, dev)
     tr.tables["KeccakPermute"] = kp
-    # KeccakPermuteControl (controller.rs:L155-L237)
-    ct = RT.Table(R.chip("KeccakPermuteControl")[0], n_events, dev)
-    ct.set("clk_high", clk >> 24); ct.set("clk_low", clk & 0xFFFFFF); ct.set("is_real", 1)
-    al = _syscall_addr_t(ct, "state_addr", addr)
-    for i in range(25):
-        ct.set("addrs.%d.value" % i, _limbs_t(addr + 8 * i)[:, :3])
-        _mem_access_t(ct, "initial_memory_access.%d" % i, pre[:, i], t_prev[:, i], clk)
-        _mem_access_t(ct, "final_memory_access.%d" % i, pre[:, i], clk, clk + 1)
-        ct.set("final_value.%d" % i, _limbs_t(post[:, i]))
-    tr.tables["KeccakPermuteControl"] = ct
+    tr.tables["KeccakPermuteControl"], al = keccak_control_table(clk, addr, pre, t_prev, post, dev)
     wa = (addr[:, None] + 8 * torch.arange(25, device=dev)[None, :]).reshape(-1)
     return _close_precompile_shard(tr, M.SYS_KECCAK_PERMUTE, clk, al, wa, t_prev.reshape(-1), (clk[:, None] + 1).expand(-1, 25).reshape(-1),
                                    pre.reshape(-1), post.reshape(-1), ctx=ctx)
+
+
+def keccak_device_tables(events77, heights):
+    """The KeccakPermute and KeccakPermuteControl tables of a Keccak shard made ON THE DEVICE from the executor's event records
+    (api.tracegen_riscv_keccak / _keccak_control): events77 = int64 [n, 77] (a CPU tensor or array is copied to the device: 616
+    bytes per call instead of 253 KB of table), heights = (KeccakPermute rows, KeccakPermuteControl rows) — what the host filler
+    gives the same shard (`precompile_shard_from`: pad32(24 n), pad32(n)). Returns the two api.ColMajor tables, which equal
+    core_real.to_col_major of the host ones word for word."""
+    from .. import api
+    ev = torch.as_tensor(events77)
+    if not ev.is_cuda:
+        ev = ev.cuda(non_blocking=True)
+    ev = ev.contiguous()
+    return api.tracegen_riscv_keccak(ev, heights[0]), api.tracegen_riscv_keccak_control(ev, heights[1])
 
 
 def _close_precompile_shard(tr, syscall_id, clk, ptr_limbs, word_addr, t_initial, t_final, v_initial, v_final, arg2_limbs=None, ctx=None):

@@ -109,6 +109,9 @@ def main():
     ap.add_argument("--device-keccak", action="store_true", help="Keccak shards: make the KeccakPermute / KeccakPermuteControl tables on the "
                     "device from the executor's event records (api.tracegen_riscv_keccak) instead of taking the tracer's; the shard's "
                     "other chips stay as they are, and the proofs are the same bytes")
+    ap.add_argument("--device-secp", action="store_true", help="secp256k1 shards: make the Secp256k1AddAssign / Secp256k1DoubleAssign table on "
+                    "the device from the executor's event records (api.tracegen_riscv_secp256k1_add / _double) instead of taking the "
+                    "tracer's; the shard's other chips stay as they are, and the proofs are the same bytes")
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--out", default="")
@@ -135,7 +138,9 @@ def main():
     t_all = time.perf_counter()
     t_prev = t_all
     keccak_events = [] if args.device_keccak and not args.dry_run else None
-    gen = X.program_shards(ex, shard_cycles, device=device, core_limit=args.core_shards or None, keccak_events=keccak_events)
+    secp_events = [] if args.device_secp and not args.dry_run else None
+    gen = X.program_shards(ex, shard_cycles, device=device, core_limit=args.core_shards or None, keccak_events=keccak_events,
+                           secp_events=secp_events)
     while True:
         try:
             kind, machine, tabs, publics, gev, sh = next(gen)
@@ -178,6 +183,14 @@ def main():
                 made = dict(zip(names, MT.keccak_device_tables(keccak_events.pop(), [int(tabs[n][1].shape[0]) for n in names])))
                 chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
                 row["device_keccak"] = True
+            if secp_events is not None and kind in ("secp256k1_add", "secp256k1_double"):
+                from sp1_amd.machines import riscv_more_trace as MT
+                name, events = secp_events.pop()
+                assert name == kind
+                chip = MT.SECP256K1_CHIPS[kind[len("secp256k1_"):]]
+                made = {chip: MT.secp256k1_device_table(kind[len("secp256k1_"):], events, int(tabs[chip][1].shape[0]))}
+                chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
+                row["device_secp"] = True
             tabs.clear()
             pv = RT.to_monty_np(publics)
             commit = pk.preprocessed_commit

@@ -516,6 +516,30 @@ int sp1hip_tracegen_riscv_keccak(uint32_t* d_table, uint32_t height, const uint6
 int sp1hip_tracegen_riscv_keccak_control(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events,
                                          sp1hip_stream_t stream);
 
+/* Device trace generation for the secp256k1 point-addition and point-doubling precompile chips, from the executor's event records as
+ * they are (sp1hip_rv64_secp256k1_add_events: n_events x 43 u64 on the device — [0] clk, [1] p_ptr, [2] q_ptr, [3 + 2i] / [4 + 2i] the
+ * previous timestamp and the word read of p word i < 8, [19 + 2i] / [20 + 2i] the same of q, [35 + i] the word written;
+ * sp1hip_rv64_secp256k1_double_events: 26 u64 — [0] clk, [1] p_ptr, [2 + 2i] / [3 + 2i] of p word i, [18 + i] the word written). The
+ * reference fills both tables on the host (crates/core/machine/src/syscall/precompiles/weierstrass/weierstrass_add.rs:L246-L330,
+ * weierstrass_double.rs:L262-L380) and has no device filler for them. Output as above: column-major [width][height] Montgomery words,
+ * one row per event.
+ *   sp1hip_tracegen_riscv_secp256k1_add     Secp256k1AddAssign, width 1599: is_real, clk_high, clk_low, two SyscallAddrOperation, 8 + 8
+ *       AddrAddOperation values, 8 + 8 MemoryAccessColsU8 (q read at clk, p rewritten at clk + 1), ten FieldOpCols in the order of
+ *       populate_field_ops (L95-L165) and the FieldLtCols of x3 and y3. x3 and y3 are computed from the words read.
+ *   sp1hip_tracegen_riscv_secp256k1_double  Secp256k1DoubleAssign, width 1591: the same with one pointer, 8 accesses (p rewritten in
+ *       place at clk) and eleven FieldOpCols (weierstrass_double.rs:L89-L160; a = 0, the constants 3 and 2 as operands).
+ * A padding row (row >= n_events) is the reference's dummy row: the field operations on p = (0, 0), q = (1, 1) (doubling: p = (0, 1)),
+ * the dummy access record in q_access[0] and q_access[4] (doubling: p_access[4]), zero elsewhere. Needs n_events <= height.
+ * Precondition, which the executor enforces before it records an event: the coordinates are reduced modulo the field's prime,
+ * q.x != p.x for an addition, p.y != 0 for a doubling. An event that breaks it neither faults nor spins — the inverse of 0 comes out
+ * as 0 — but its row satisfies no constraint system. All argument checks come before any launch; a null pointer is accepted only with
+ * a zero count / height; height == 0 succeeds without a launch. The calls enqueue and return: they do not synchronise. */
+int sp1hip_tracegen_riscv_secp256k1_add_width(void);      /* 1599 */
+int sp1hip_tracegen_riscv_secp256k1_double_width(void);   /* 1591 */
+int sp1hip_tracegen_riscv_secp256k1_add(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_secp256k1_double(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events,
+                                           sp1hip_stream_t stream);
+
 /* ---------------------------------------------------------------- guest execution (host code, no device work)
  * An rv64im executor for SP1 guest ELFs: what `MinimalExecutor` + `TracingVM` do for the core prover
  * (/root/reference/crates/core/executor/src/minimal.rs, tracing.rs:L57-L147, vm.rs:L139-L431; the controller's shard loop is

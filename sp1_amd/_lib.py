@@ -241,6 +241,10 @@ PROTOTYPES = [
     ("sp1hip_tracegen_riscv_keccak_control_width", None, []),
     ("sp1hip_tracegen_riscv_keccak", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_keccak_control", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_secp256k1_add_width", None, []),
+    ("sp1hip_tracegen_riscv_secp256k1_double_width", None, []),
+    ("sp1hip_tracegen_riscv_secp256k1_add", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_secp256k1_double", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_rv64_create", None, [u8p, C.c_uint64, C.POINTER(_vp)]),
     ("sp1hip_rv64_destroy", "void", [_vp]),
     ("sp1hip_rv64_write_stdin", None, [_vp, u8p, C.c_uint64]),

@@ -596,6 +596,31 @@ def tracegen_riscv_keccak_control(events, height, stream=None):
     return _tracegen_keccak("sp1hip_tracegen_riscv_keccak_control", events, height, stream)
 
 
+SECP_ADD_EVENT_WORDS, SECP_DOUBLE_EVENT_WORDS = 43, 26                              # SP1HIP_RV64_SECP_ADD_WORDS, _DOUBLE_WORDS
+
+
+def _tracegen_secp(fn, words, events, height, stream):
+    width = getattr(_L(), fn + "_width")()
+    n = int(events.shape[0])
+    assert events.dtype == torch.int64 and (n == 0 or (events.is_cuda and events.shape[1] == words and events.is_contiguous()))
+    out = device_words(width * int(height))
+    check(getattr(_L(), fn)(_dptr(out), int(height), _dptr(events) if n else None, n, _stream_ptr(stream)))
+    return ColMajor(out, int(height), width)
+
+
+def tracegen_riscv_secp256k1_add(events, height, stream=None):
+    """`generate_trace_device` for the Secp256k1AddAssign chip (sp1hip_tracegen_riscv_secp256k1_add): events = a device int64 tensor
+    [n, 43] of the executor's SECP256K1_ADD records (riscv_exec.ExecutedShard.secp256k1_add); one row per event, height >= n,
+    padding rows = the reference's dummy row. Returns the column-major [1599][height] table as a ColMajor."""
+    return _tracegen_secp("sp1hip_tracegen_riscv_secp256k1_add", SECP_ADD_EVENT_WORDS, events, height, stream)
+
+
+def tracegen_riscv_secp256k1_double(events, height, stream=None):
+    """The same for the Secp256k1DoubleAssign chip (sp1hip_tracegen_riscv_secp256k1_double): events int64 [n, 26]
+    (ExecutedShard.secp256k1_double); column-major [1591][height]."""
+    return _tracegen_secp("sp1hip_tracegen_riscv_secp256k1_double", SECP_DOUBLE_EVENT_WORDS, events, height, stream)
+
+
 class ProvingKey:
     """`ProvingKey` of the AirProver slot: the preprocessed commitment round + the verifying key (sp1hip_setup).
     Keeps the preprocessed device tables alive."""

@@ -20,6 +20,7 @@
 // the table's write. Padding rows run the same code on the zero state (trace.rs:L88-L122: a trailing chunk takes the first rows
 // of the zero state's permutation, so padding row q is its round q mod 24) with is_real = 0.
 #include "device_ctx.hpp"
+#include "tg_field_op.hpp"
 
 namespace sp1hip {
 namespace tgk {
@@ -45,23 +46,9 @@ template <int N> __device__ __forceinline__ uint64_t rotl(uint64_t v) {
     if constexpr (N == 0) return v; else return (v << N) | (v >> (64 - N));
 }
 
-// The cursor a lane writes its row with: one column per put(), in table order. The word index is (size_t) col * height + row
-// (a full shard's table passes 2^30 bytes), kept as a running sum.
-struct Cursor {
-    uint32_t* out;
-    size_t at, height;
-    __device__ __forceinline__ void word(uint32_t w) { gptr(out)[at] = w; at += height; }
-    __device__ __forceinline__ void bit(bool b) { word(b ? kb::R1 : 0u); }                     // 0 or the Montgomery form of 1: a select
-    __device__ __forceinline__ void val(uint32_t canonical) { word(kb::to_monty(canonical)); }
-    __device__ __forceinline__ void limbs(uint64_t v, int n = 4) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) if (i < n) val((uint32_t)(v >> (16 * i)) & 0xffffu);
-    }
-    __device__ __forceinline__ void bits64(uint64_t v) {
-#pragma unroll 8
-        for (int z = 0; z < 64; z++) bit((v >> z) & 1);
-    }
-};
+// The cursor a lane writes its row with (one column per put, in table order) is tg_field_op.hpp's, as are the memory columns below.
+using tgf::Cursor;
+using tgf::memory_access;
 
 // a[x + 5 y]: theta's column parities c and c', a' = a ^ c ^ c' (p3-keccak-air's names; sp1_amd/machines/riscv_more_trace.py keccak_f_rows)
 __device__ __forceinline__ void theta(const uint64_t (&a)[25], uint64_t (&c)[5], uint64_t (&cp)[5]) {
@@ -139,20 +126,6 @@ __global__ __launch_bounds__(256) void keccak_permute_kernel(uint32_t* __restric
     w.bit(real);
 }
 
-// MemoryAccessCols: prev_value[4], prev_high, prev_low, compare_low, diff_low_limb, diff_high_limb. The difference to the previous
-// access is taken on the low 24 bits when both stand in the same 2^24 window, on the high limbs otherwise.
-__device__ __forceinline__ void memory_access(Cursor& w, uint64_t prev_value, uint64_t t_prev, uint64_t t_cur) {
-    const uint32_t ph = (uint32_t)(t_prev >> 24), pl = (uint32_t)t_prev & 0xffffffu, ch = (uint32_t)(t_cur >> 24), cl = (uint32_t)t_cur & 0xffffffu;
-    const bool same = ph == ch;
-    const uint32_t d = (same ? cl - pl : ch - ph) - 1u;
-    w.limbs(prev_value);
-    w.val(ph);
-    w.val(pl);
-    w.bit(same);
-    w.val(d & 0xffffu);
-    w.val(d >> 16);
-}
-
 __global__ __launch_bounds__(256) void keccak_control_kernel(uint32_t* __restrict__ out, uint32_t height, const uint64_t* __restrict__ events, uint32_t n_events) {
     const uint32_t row = blockIdx.x * 256u + threadIdx.x;
     if (row >= height) return;
@@ -165,15 +138,8 @@ __global__ __launch_bounds__(256) void keccak_control_kernel(uint32_t* __restric
     const uint64_t clk = gptr(ev)[0], addr = gptr(ev)[1];
     w.val((uint32_t)(clk >> 24));
     w.val((uint32_t)clk & 0xffffffu);
-    // SyscallAddrOperation: addr[3], top_two_limb_min = (addr[1] + addr[2])^-1, IsZero(addr[1] + addr[2] - 2 * 0xffff)
-    w.limbs(addr, 3);
-    const uint32_t top = ((uint32_t)(addr >> 16) & 0xffffu) + ((uint32_t)(addr >> 32) & 0xffffu);
-    w.word(kb::inv(kb::to_monty(top)));                                                          // 0 for 0
-    const uint32_t dmax = top == 2u * 0xffffu ? 0u : kb::P - (2u * 0xffffu - top);
-    w.word(kb::inv(kb::to_monty(dmax)));
-    w.bit(dmax == 0);
-    // AddrAddOperation x 25: the low three limbs of addr + 8 i
-    for (uint32_t i = 0; i < 25; i++) w.limbs(addr + 8u * i, 3);
+    tgf::syscall_addr(w, addr);                                                                 // SyscallAddrOperation
+    for (uint32_t i = 0; i < 25; i++) tgf::addr_add(w, addr + 8u * i);                          // AddrAddOperation x 25
     w.bit(true);                                                                                // is_real
     // the reads at clk against the words' previous accesses, the writes at clk + 1 against the reads
     for (uint32_t i = 0; i < 25; i++) memory_access(w, gptr(ev)[3 + 2 * i], gptr(ev)[2 + 2 * i], clk);

@@ -439,14 +439,16 @@ def split_thresholds(program_rows):
     return out
 
 
-def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_events=None):
+def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_events=None, secp_events=None):
     """Every shard of a run, in the order the reference's controller emits them: the core shards as the program executes
     (`(kind, machine, tables, publics, global events, ExecutedShard)` with kind = "core"), then one precompile shard for the
     KECCAK_PERMUTE, POSEIDON2, SHA_EXTEND and SHA_COMPRESS calls each if there were any ("keccak", "poseidon2", "sha_extend",
     "sha_compress"), then the memory shard: MemoryGlobalInit / MemoryGlobalFinalize over
     every address the run touched ("memory"). The global events of all shards cancel as a multiset: that is the statement the
     shards' septic-curve digests add up to. `core_limit`: only the first so many core shards are traced and yielded (the rest of
-    the program still runs, so every precompile and memory shard is there)."""
+    the program still runs, so every precompile and memory shard is there). `keccak_events` / `secp_events`: a list that takes,
+    per Keccak / secp256k1 shard yielded, the shard's event records (for secp256k1 a pair (kind, events)) — what device trace
+    generation makes the chip's table from."""
     from . import riscv_more_trace as MT
     keccak, poseidon2, sha_extend, sha_compress, uint256, secp_add, secp_double = [], [], [], [], [], [], []
     families = {}
@@ -504,6 +506,8 @@ def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_e
                              ("secp256k1_double", secp_double, MT.secp256k1_double_shard_from)):
         for part in chunks(name, evs):
             machine, tables, publics, gev = build(part, device, ctx=ctx)
+            if secp_events is not None and name.startswith("secp256k1_"):
+                secp_events.append((name, part))
             yield name, machine, tables, publics, gev, None
     for kind in FAMILIES:                                    # one chip per kind; Fp / UINT256 kinds hold all their system calls' events
         for part in chunks(kind, families.get(kind)):

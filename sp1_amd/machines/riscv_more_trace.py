@@ -848,16 +848,13 @@ _word256 = lambda ws: sum(int(x) << (64 * i) for i, x in enumerate(ws))
 _low_bytes = lambda v: torch.stack([(v >> (16 * k)) & 0xFF for k in range(4)], dim=1)
 
 
-def secp256k1_add_shard_from(events, device="cpu", ctx=None):
-    """The SECP256K1_ADD precompile shard of the executor's events ([n, 43] int64): Secp256k1AddAssign rows (`populate_row` and
-    the dummy row of `generate_trace_into`, weierstrass_add.rs:L246-L330, L612-L680), SyscallPrecompile, MemoryLocal, Global, Byte, Range."""
-    dev = torch.device(device)
+def secp256k1_add_table(events, dev):
+    """The Secp256k1AddAssign table of the executor's events ([n, 43] int64), padding rows included (`populate_row` and the dummy row
+    of `generate_trace_into`, weierstrass_add.rs:L246-L330, L612-L680). Returns the table, the events as a tensor, the two pointers' limbs."""
     ev = np.asarray(events).astype(np.uint64)
     n = ev.shape[0]
     air = R.chip("Secp256k1AddAssign")[0]
     L = air.layout
-    tr = RT.Tracer.__new__(RT.Tracer)
-    tr.dev, tr.tables = dev, {}
     tb = RT.Table(air, n, dev)
     rows = np.zeros((tb.main.shape[0], air.main_width), dtype=np.int64)
     coord = lambda cols: [_word256(w) for w in ev[:, cols]]
@@ -883,6 +880,19 @@ def secp256k1_add_shard_from(events, device="cpu", ctx=None):
         tb.set("p_access.%d.prev_value_u8.low_bytes" % i, _low_bytes(ps[:, i, 1]))
         _mem_access_t(tb, "q_access.%d.memory_access" % i, qs[:, i, 1], qs[:, i, 0], clk)
         tb.set("q_access.%d.prev_value_u8.low_bytes" % i, _low_bytes(qs[:, i, 1]))
+    return tb, t, pl, ql
+
+
+def secp256k1_add_shard_from(events, device="cpu", ctx=None):
+    """The SECP256K1_ADD precompile shard of the executor's events ([n, 43] int64): Secp256k1AddAssign rows (secp256k1_add_table),
+    SyscallPrecompile, MemoryLocal, Global, Byte, Range."""
+    dev = torch.device(device)
+    tr = RT.Tracer.__new__(RT.Tracer)
+    tr.dev, tr.tables = dev, {}
+    tb, t, pl, ql = secp256k1_add_table(events, dev)
+    n = t.shape[0]
+    clk, pp, qp = t[:, 0], t[:, 1], t[:, 2]
+    ps, qs = t[:, 3:19].reshape(n, 8, 2), t[:, 19:35].reshape(n, 8, 2)
     tr.tables["Secp256k1AddAssign"] = tb
     eight = torch.arange(8, device=dev)[None, :]
     wa = torch.cat([(pp[:, None] + 8 * eight).reshape(-1), (qp[:, None] + 8 * eight).reshape(-1)])
@@ -893,16 +903,13 @@ def secp256k1_add_shard_from(events, device="cpu", ctx=None):
     return _close_precompile_shard(tr, M.SYS_SECP256K1_ADD, clk, pl, wa, t_i, t_f, v_i, v_f, arg2_limbs=ql, ctx=ctx)
 
 
-def secp256k1_double_shard_from(events, device="cpu", ctx=None):
-    """The SECP256K1_DOUBLE precompile shard of the executor's events ([n, 26] int64): Secp256k1DoubleAssign rows
-    (weierstrass_double.rs:L262-L380: the point is rewritten in place at clk), SyscallPrecompile, MemoryLocal, Global, Byte, Range."""
-    dev = torch.device(device)
+def secp256k1_double_table(events, dev):
+    """The Secp256k1DoubleAssign table of the executor's events ([n, 26] int64), padding rows included (weierstrass_double.rs:L262-L380:
+    the point is rewritten in place at clk). Returns the table, the events as a tensor, the pointer's limbs."""
     ev = np.asarray(events).astype(np.uint64)
     n = ev.shape[0]
     air = R.chip("Secp256k1DoubleAssign")[0]
     L = air.layout
-    tr = RT.Tracer.__new__(RT.Tracer)
-    tr.dev, tr.tables = dev, {}
     tb = RT.Table(air, n, dev)
     rows = np.zeros((tb.main.shape[0], air.main_width), dtype=np.int64)
     coord = lambda cols: [_word256(w) for w in ev[:, cols]]
@@ -923,11 +930,40 @@ def secp256k1_double_shard_from(events, device="cpu", ctx=None):
         tb.set("p_addrs.%d.value" % i, _limbs_t(pp + 8 * i)[:, :3])
         _mem_access_t(tb, "p_access.%d.memory_access" % i, ps[:, i, 1], ps[:, i, 0], clk)
         tb.set("p_access.%d.prev_value_u8.low_bytes" % i, _low_bytes(ps[:, i, 1]))
+    return tb, t, pl
+
+
+def secp256k1_double_shard_from(events, device="cpu", ctx=None):
+    """The SECP256K1_DOUBLE precompile shard of the executor's events ([n, 26] int64): Secp256k1DoubleAssign rows
+    (secp256k1_double_table), SyscallPrecompile, MemoryLocal, Global, Byte, Range."""
+    dev = torch.device(device)
+    tr = RT.Tracer.__new__(RT.Tracer)
+    tr.dev, tr.tables = dev, {}
+    tb, t, pl = secp256k1_double_table(events, dev)
+    n = t.shape[0]
+    clk, pp = t[:, 0], t[:, 1]
+    ps = t[:, 2:18].reshape(n, 8, 2)
     tr.tables["Secp256k1DoubleAssign"] = tb
     eight = torch.arange(8, device=dev)[None, :]
     wa = (pp[:, None] + 8 * eight).reshape(-1)
     return _close_precompile_shard(tr, M.SYS_SECP256K1_DOUBLE, clk, pl, wa, ps[:, :, 0].reshape(-1), clk[:, None].expand(-1, 8).reshape(-1),
                                    ps[:, :, 1].reshape(-1), t[:, 18:26].reshape(-1), ctx=ctx)
+
+
+SECP256K1_CHIPS = {"add": "Secp256k1AddAssign", "double": "Secp256k1DoubleAssign"}
+
+
+def secp256k1_device_table(kind, events, height):
+    """The Secp256k1AddAssign (kind "add", events int64 [n, 43]) or Secp256k1DoubleAssign ("double", [n, 26]) table of a secp256k1
+    shard made ON THE DEVICE from the executor's event records (api.tracegen_riscv_secp256k1_add / _double). A CPU tensor or
+    array is copied to the device: 344 / 208 bytes per call instead of 6.4 KB of table. height = what the host filler gives the same
+    shard (pad32(n)). Returns the api.ColMajor table, which equals core_real.to_col_major of the host one word for word."""
+    from .. import api
+    ev = torch.as_tensor(np.ascontiguousarray(events) if isinstance(events, np.ndarray) else events)
+    if not ev.is_cuda:
+        ev = ev.cuda(non_blocking=True)
+    ev = ev.contiguous()
+    return {"add": api.tracegen_riscv_secp256k1_add, "double": api.tracegen_riscv_secp256k1_double}[kind](ev, height)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -202,13 +202,49 @@ static inline std::array<E, 3> zc_sum_y(const ZcPoly<K>& p, const std::vector<E>
     return {y0, y2, y4};
 }
 
+// What the second round's sum at node 0 holds of the constraints' values ON REAL ROWS of the base table `p`, a0 the first round's
+// challenge: the folded row 2 q is row 4 q + a0 (row 4 q + 1 - row 4 q), and a constraint of degree <= 3 along it is the cubic
+// through its values at 0, 1, 2, 4 — of which the values at 0 and 1 are the constraint on rows 4 q and 4 q + 1 themselves:
+//   sum_q eq[q] (C_0(a0) C(row 4 q) + C_1(a0) C(row 4 q + 1)),  C_0(X) = (X - 1)(X - 2)(X - 4) / -8,  C_1(X) = X (X - 2)(X - 4) / 3
+// Zero on a satisfying trace. A prover that takes the first TWO rounds from one pass over the base table (sp1_amd/csrc/zerocheck.hip,
+// zc_biv_*) leaves these values out, as every prover leaves them out of node 0 of the first round (FIRST above); zerocheck_prove
+// subtracts this sum when asked to restate that prover (`two_round_form`), so that the two can be compared on tables that do not
+// satisfy the constraints. A padded row's value (the constant C(0)) stays in: it cancels against the geq term either way.
+static inline E zc_real_row_values_in_round1_node0(const ZcPoly<F>& p, const E& a0) {
+    if (p.real_rows == 0 || p.zeta.size() < 2) return E::zero();
+    const int w = p.air->main_width, wp = p.air->prep_width;
+    std::vector<E> eq = partial_lagrange(std::vector<E>(p.zeta.begin(), p.zeta.end() - 2));
+    const E one = E::one(), two = E::from_base(F::two()), four = E::from_base(F::from_canonical(4));
+    const E tail = (a0 - two) * (a0 - four);
+    const E c0 = (a0 - one) * tail * einv(E::zero() - E::from_base(F::from_canonical(8)));
+    const E c1 = a0 * tail * einv(E::from_base(F::from_canonical(3)));
+    const size_t quads = (p.real_rows + 3) / 4;
+    E total = E::zero();
+#pragma omp parallel
+    {
+        E local = E::zero();
+#pragma omp for schedule(static) nowait
+        for (size_t q = 0; q < quads; q++)
+            for (size_t y = 0; y < 2; y++) {
+                const size_t row = 4 * q + y;
+                if (row >= p.real_rows) continue;
+                const E v = eval_constraints<F>(*p.air, p.prep.data() + row * wp, p.main.data() + row * w, p.publics, p.alpha_pows.data());
+                local += v * (y ? c1 : c0) * eq[q];
+            }
+#pragma omp critical
+        total += local;
+    }
+    return total;
+}
+
 template <class K, bool FIRST>
-static inline UniPoly zc_sum_as_poly(const ZcPoly<K>& p, const E& claim) {
+static inline UniPoly zc_sum_as_poly(const ZcPoly<K>& p, const E& claim, const E& left_out_of_node0 = E::zero()) {
     if (p.real_rows == 0) return UniPoly(5, E::zero());
     std::vector<E> rest(p.zeta.begin(), p.zeta.end() - 1);
     const E last = p.zeta.back();
     std::vector<E> eq = partial_lagrange(rest);
     auto y = zc_sum_y<K, FIRST>(p, eq);
+    y[0] = y[0] - left_out_of_node0;
     const size_t threshold_half = (p.real_rows + 1) / 2 - 1;
     E msb = threshold_half < ((size_t)1 << (p.num_vars - 1)) ? p.eq_adjustment * eq[threshold_half] : E::zero();
     const E four = E::from_base(F::from_canonical(4)), two = E::from_base(F::two());
@@ -287,7 +323,7 @@ struct ZcProof {
 
 static inline ZcProof zerocheck_prove(const std::vector<ZcChipInput>& chips, int max_log_row_count, const std::vector<E>& zeta,
                                       const E& batching_challenge, const E& gkr_batch, const std::vector<F>& publics,
-                                      Challenger& ch) {
+                                      Challenger& ch, bool two_round_form = false) {
     int max_constraints = 0;
     for (auto& c : chips) max_constraints = std::max(max_constraints, c.air->num_constraints);
     std::vector<E> pows(max_constraints);
@@ -332,7 +368,9 @@ static inline ZcProof zerocheck_prove(const std::vector<ZcChipInput>& chips, int
     for (int r = 1; r < max_log_row_count; r++) {
         std::vector<E> round_claims;
         for (auto& u : uni) round_claims.push_back(uni_eval(u, point.front()));
-        for (size_t i = 0; i < cur.size(); i++) uni[i] = zc_sum_as_poly<E, false>(cur[i], round_claims[i]);
+        // (two_round_form: zc_real_row_values_in_round1_node0)
+        for (size_t i = 0; i < cur.size(); i++)
+            uni[i] = zc_sum_as_poly<E, false>(cur[i], round_claims[i], two_round_form && r == 1 ? zc_real_row_values_in_round1_node0(polys[i], point.front()) : E::zero());
         rlc = rlc_univariate(uni, lambda);
         for (auto& c : rlc) ch.observe_ext(c);
         proof.univariate_polys.push_back(rlc);

@@ -239,6 +239,11 @@ static std::vector<ZcAir> make_airs(int n, const uint32_t** progs, const int* pr
     return airs;
 }
 
+// 1: orc_zerocheck_prove restates the prover that takes the first two rounds from one pass over the base tables (kb_zerocheck.hpp,
+// zc_real_row_values_in_round1_node0): the same bytes on a satisfying trace, comparable with that prover on any other table
+static int g_zc_two_round_form = 0;
+void orc_set_zc_two_round_form(int on) { g_zc_two_round_form = on; }
+
 // openings: per chip main evals then prep evals (ext), flattened. Returns blob size.
 size_t orc_zerocheck_prove(int n_chips, const uint32_t** progs, const int* prog_lens, const int* main_w, const int* prep_w,
                            const int* n_constraints, const uint32_t** mains, const uint32_t** preps, const uint64_t* real_rows,
@@ -260,7 +265,8 @@ size_t orc_zerocheck_prove(int n_chips, const uint32_t** progs, const int* prog_
     memcpy(z.data(), zeta, (size_t)max_log_row_count * 16);
     std::vector<F> pv(n_publics);
     memcpy(pv.data(), publics, (size_t)n_publics * 4);
-    ZcProof p = zerocheck_prove(chips, max_log_row_count, z, load_e(alpha), load_e(gkr), pv, *static_cast<Challenger*>(challenger));
+    ZcProof p = zerocheck_prove(chips, max_log_row_count, z, load_e(alpha), load_e(gkr), pv, *static_cast<Challenger*>(challenger),
+                                g_zc_two_round_form != 0 && max_log_row_count >= 2);
     std::vector<uint8_t> b = serialize_zc_proof(p);
     if (b.size() <= cap) memcpy(out, b.data(), b.size());
     return b.size();

@@ -97,6 +97,8 @@ def lib():
         L.orc_shard_verify_pv.argtypes = L.orc_shard_verify.argtypes + [u32p, C.c_int, C.c_int, u32p, C.c_int, C.c_int, C.c_int]
         L.orc_stage_seconds.argtypes = [C.POINTER(C.c_double)]
         L.orc_set_gkr_sparse.argtypes = [C.c_int]
+        L.orc_set_zc_two_round_form.argtypes = [C.c_int]
+        L.orc_set_zc_two_round_form.restype = None
         L.orc_set_threads.argtypes = [C.c_int]
         L.orc_set_threads.restype = None
         _lib = L
@@ -486,7 +488,10 @@ def _zc_common(chips):
     return n, progs, lens, mw, pw, nc
 
 
-def zerocheck_prove(chips, max_log_row_count, zeta, alpha, gkr, publics, challenger):
+def zerocheck_prove(chips, max_log_row_count, zeta, alpha, gkr, publics, challenger, two_round_form=False):
+    """two_round_form: restate the prover that takes rounds 0 and 1 from one pass over the base tables — the constraints' values on
+    real rows are left out of round 1's node 0 as they are out of round 0's (kb_zerocheck.hpp). The same bytes on a satisfying
+    trace; on any other table, what that prover gives (max_log_row_count >= 2; with one variable there is no second round)."""
     L = lib()
     L.orc_zerocheck_prove.restype = C.c_size_t
     n, progs, lens, mw, pw, nc = _zc_common(chips)
@@ -498,9 +503,13 @@ def zerocheck_prove(chips, max_log_row_count, zeta, alpha, gkr, publics, challen
     args = [n, progs, lens, mw, pw, nc, mains, preps, rows, _p(openings), max_log_row_count, _p(zeta), _p(alpha), _p(gkr),
             _p(publics) if publics.size else None, int(publics.size)]
     probe = challenger.clone()
-    size = L.orc_zerocheck_prove(*args, C.c_void_p(probe.h), None, C.c_size_t(0))
-    buf = (C.c_uint8 * size)()
-    got = L.orc_zerocheck_prove(*args, C.c_void_p(challenger.h), buf, C.c_size_t(size))
+    L.orc_set_zc_two_round_form(1 if two_round_form else 0)
+    try:
+        size = L.orc_zerocheck_prove(*args, C.c_void_p(probe.h), None, C.c_size_t(0))
+        buf = (C.c_uint8 * size)()
+        got = L.orc_zerocheck_prove(*args, C.c_void_p(challenger.h), buf, C.c_size_t(size))
+    finally:
+        L.orc_set_zc_two_round_form(0)
     assert got == size
     return bytes(buf)
 

@@ -8,9 +8,10 @@ programs differ most from the secp256k1 / UINT256_MUL chips that tests/test_gpu_
     ed_decompress   FieldSqrtCols (a FieldOpCols checked against another operation's result), one-coefficient operands
     uint256_ops     a + b + c / a * b + c with carry: five memory slices, three register reads, modulus 2^256
 
-The file sorts last on purpose: it was written when the round's GPU minutes were spent (the CPU side — every constraint on every
-row, every bus, the zerocheck planner's compiled program against the SSA — is tests/test_riscv_precompiles.py and
-tests/test_zc_compiler.py), so its first run is the driver's; a failure here does not hide the rest of the suite behind `-x`."""
+The file sorts last on purpose: these are the longest programs the suite proves, and a failure here does not hide the rest of the
+suite behind `-x` (the CPU side — every constraint on every row, every bus, the zerocheck planner's compiled program against the
+SSA — is tests/test_riscv_precompiles.py and tests/test_zc_compiler.py). It has run on an MI355X with the rest of `-m gpu` since;
+the fused pieces these shards go through are held on arbitrary tables by tests/test_gpu_zc_pieces.py."""
 import pytest
 
 pytestmark = pytest.mark.gpu

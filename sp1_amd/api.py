@@ -554,7 +554,8 @@ def tracegen_riscv_global(events, height, stream=None):
     return ColMajor(out, int(height), 241)
 
 
-RISCV_ALU_CHIPS = {"Add": 0, "Addi": 1, "Sub": 2, "Addw": 3, "Subw": 4, "Mul": 5, "ShiftRight": 6, "Branch": 7}   # SP1HIP_RV64_CHIP_*
+RISCV_ALU_CHIPS = {"Add": 0, "Addi": 1, "Sub": 2, "Addw": 3, "Subw": 4, "Mul": 5, "ShiftRight": 6, "Branch": 7,    # SP1HIP_RV64_CHIP_*
+                   "Bitwise": 8, "Lt": 9, "ShiftLeft": 10, "UType": 11, "Jal": 12, "Jalr": 13}
 ALU_EVENT_WORDS = 11                                                                 # sp1hip_rv64_alu_event_t: 11 u64
 
 

@@ -112,6 +112,9 @@ def main():
     ap.add_argument("--device-secp", action="store_true", help="secp256k1 shards: make the Secp256k1AddAssign / Secp256k1DoubleAssign table on "
                     "the device from the executor's event records (api.tracegen_riscv_secp256k1_add / _double) instead of taking the "
                     "tracer's; the shard's other chips stay as they are, and the proofs are the same bytes")
+    ap.add_argument("--device-core", action="store_true", help="core shards: make the tables of the fourteen ALU / branch / jump chips and the "
+                    "nine load and store chips on the device from the shard's event records (riscv_exec.core_device_tables) instead of "
+                    "taking the tracer's; the shard's other chips stay as they are, and the proofs are the same bytes")
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--out", default="")
@@ -191,6 +194,10 @@ def main():
                 made = {chip: MT.secp256k1_device_table(kind[len("secp256k1_"):], events, int(tabs[chip][1].shape[0]))}
                 chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
                 row["device_secp"] = True
+            if args.device_core and kind == "core":
+                made = X.core_device_tables(sh.events, {a.name: int(tabs[a.name][1].shape[0]) for a, _ in machine})
+                chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
+                row["device_core"], row["device_core_chips"] = True, len(made)
             tabs.clear()
             pv = RT.to_monty_np(publics)
             commit = pk.preprocessed_commit

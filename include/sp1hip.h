@@ -502,6 +502,29 @@ int sp1hip_tracegen_riscv_alu_width(int chip);       /* columns of the chip's ta
 int sp1hip_tracegen_riscv_alu(int chip, uint32_t* d_table, uint32_t height, const sp1hip_rv64_alu_event_t* d_events, uint32_t n_events,
                               sp1hip_stream_t stream);
 
+/* Device trace generation for the nine load and store chips of a core shard: LoadByte, LoadHalf, LoadWord, LoadDouble, LoadX0 (a
+ * load whose destination is x0), StoreByte, StoreHalf, StoreWord, StoreDouble — `event_to_row` of the reference's
+ * crates/core/machine/src/memory/instructions/{load,store}/ with CPUState, the I register adapter, AddressOperation
+ * (operations/address.rs) and MemoryAccessCols (memory/consistency/{columns,trace}.rs). An event is the instruction's
+ * `MemInstrEvent` with its register access records and its memory record, flattened to twelve words (96 bytes; a row is 156-200):
+ *   ops    = opcode | op_a << 8 | op_b << 16   (register numbers; Opcode as in opcode.rs), as in sp1hip_rv64_alu_event_t
+ *   b      = the value of the base register, imm = the I-type immediate (op_c_imm), sign-extended
+ *   a_prev = the value op_a held before (for a store: the value stored), a_pts / b_pts = the registers' previous timestamps
+ *   m_addr = the byte address b + imm; m_pts / m_prev = the timestamp and content of its 8-byte word's previous access;
+ *   m_new  = the word's content afterwards (= m_prev for a load). These three travel as the executor recorded them: the device
+ *            does not re-derive what the instruction does to memory.
+ * The memory access stands at clk + 1, the accesses of op_b and op_a at clk + 3 and clk + 4. Writes the column-major
+ * [width][height] table in Montgomery words; rows >= n_events are zero rows, the padding of all nine chips. A register access across
+ * a 2^24 clock boundary compares against 0 as above (its MemoryBump row stays with the caller); the memory access itself needs no
+ * such row. */
+typedef struct { uint64_t pc, clk, ops, b, imm, a_prev, a_pts, b_pts, m_addr, m_pts, m_prev, m_new; } /* 96 bytes */ sp1hip_rv64_mem_event_t;
+typedef enum { SP1HIP_RV64_MEM_CHIP_LOAD_BYTE = 0, SP1HIP_RV64_MEM_CHIP_LOAD_HALF = 1, SP1HIP_RV64_MEM_CHIP_LOAD_WORD = 2,
+               SP1HIP_RV64_MEM_CHIP_LOAD_DOUBLE = 3, SP1HIP_RV64_MEM_CHIP_LOAD_X0 = 4, SP1HIP_RV64_MEM_CHIP_STORE_BYTE = 5,
+               SP1HIP_RV64_MEM_CHIP_STORE_HALF = 6, SP1HIP_RV64_MEM_CHIP_STORE_WORD = 7, SP1HIP_RV64_MEM_CHIP_STORE_DOUBLE = 8 } sp1hip_rv64_mem_chip;
+int sp1hip_tracegen_riscv_mem_width(int chip);       /* columns of the chip's table; -1 for an unknown chip */
+int sp1hip_tracegen_riscv_mem(int chip, uint32_t* d_table, uint32_t height, const sp1hip_rv64_mem_event_t* d_events, uint32_t n_events,
+                              sp1hip_stream_t stream);
+
 /* Device trace generation for the two chips of a KECCAK_PERMUTE precompile shard, from the executor's event records as they are
  * (sp1hip_rv64_keccak_events below: n_events x 77 u64 on the device — [0] clk, [1] state pointer, [2 + 2i] / [3 + 2i] the previous
  * timestamp and the word read of state word i < 25, [52 + i] the word written). The reference fills both tables on the host

@@ -89,6 +89,11 @@ class Rv64AluEvent(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("pc", "clk", "ops", "a", "b", "c", "a_prev", "a_pts", "b_pts", "c_pts", "aux")]
 
 
+class Rv64MemEvent(C.Structure):
+    """sp1hip_rv64_mem_event_t: what sp1hip_tracegen_riscv_mem makes a row of (riscv_exec.pack_mem_events builds arrays of them)."""
+    _fields_ = [(n, C.c_uint64) for n in ("pc", "clk", "ops", "b", "imm", "a_prev", "a_pts", "b_pts", "m_addr", "m_pts", "m_prev", "m_new")]
+
+
 class Vk(C.Structure):
     _fields_ = [("pc_start", C.c_uint32 * 3), ("initial_global_cumulative_sum", C.c_uint32 * 14),
                 ("preprocessed_commit", C.c_uint32 * 8), ("enable_untrusted_programs", C.c_uint32)]
@@ -237,6 +242,8 @@ PROTOTYPES = [
     ("sp1hip_tracegen_riscv_global", None, [_vp, C.c_uint64, _vp, C.c_uint64, _vp]),
     ("sp1hip_tracegen_riscv_alu_width", None, [C.c_int]),
     ("sp1hip_tracegen_riscv_alu", None, [C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_mem_width", None, [C.c_int]),
+    ("sp1hip_tracegen_riscv_mem", None, [C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_keccak_width", None, []),
     ("sp1hip_tracegen_riscv_keccak_control_width", None, []),
     ("sp1hip_tracegen_riscv_keccak", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),

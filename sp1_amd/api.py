@@ -572,6 +572,24 @@ def tracegen_riscv_alu(chip, events, height, stream=None):
     return ColMajor(out, int(height), width)
 
 
+RISCV_MEM_CHIPS = {"LoadByte": 0, "LoadHalf": 1, "LoadWord": 2, "LoadDouble": 3, "LoadX0": 4,                     # SP1HIP_RV64_MEM_CHIP_*
+                   "StoreByte": 5, "StoreHalf": 6, "StoreWord": 7, "StoreDouble": 8}
+MEM_EVENT_WORDS = 12                                                                 # sp1hip_rv64_mem_event_t: 12 u64
+
+
+def tracegen_riscv_mem(chip, events, height, stream=None):
+    """`generate_trace_device` for one of the load and store chips of RISCV_MEM_CHIPS (sp1hip_tracegen_riscv_mem): events = a
+    device int64 tensor [n, 12] of sp1hip_rv64_mem_event_t records (riscv_exec.pack_mem_events); returns the column-major table
+    [width][height] as a ColMajor."""
+    kind = RISCV_MEM_CHIPS[chip]
+    width = _L().sp1hip_tracegen_riscv_mem_width(kind)
+    n = int(events.shape[0])
+    assert events.dtype == torch.int64 and (n == 0 or (events.shape[1] == MEM_EVENT_WORDS and events.is_contiguous()))
+    out = device_words(width * int(height))
+    check(_L().sp1hip_tracegen_riscv_mem(kind, _dptr(out), int(height), _dptr(events) if n else None, n, _stream_ptr(stream)))
+    return ColMajor(out, int(height), width)
+
+
 KECCAK_EVENT_WORDS = 77                                                              # SP1HIP_RV64_KECCAK_WORDS
 
 

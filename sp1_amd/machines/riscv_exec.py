@@ -385,6 +385,44 @@ def pack_alu_events(events, chip=None):
     return xp.stack(cols, 1) if xp is np else torch.stack(cols, dim=1).contiguous()
 
 
+MEM_TRACEGEN_CHIPS = ("LoadByte", "LoadHalf", "LoadWord", "LoadDouble", "LoadX0",           # api.RISCV_MEM_CHIPS: tables made on the device
+                      "StoreByte", "StoreHalf", "StoreWord", "StoreDouble")
+
+
+def pack_mem_events(events, chip=None):
+    """The executor's 20-word instruction events -> `sp1hip_rv64_mem_event_t` records (include/sp1hip.h: 12 u64 words — pc, clk,
+    ops, b, imm, a_prev, a_pts, b_pts, m_addr, m_pts, m_prev, m_new) for the load and store chips whose tables the device generates
+    (api.tracegen_riscv_mem), in the events' order = the tables' row order. `events`: [n, 20] int64 (numpy or torch; all of a
+    shard's events when `chip` names the chip to select, else already that chip's). An event is 96 bytes where the row it becomes
+    is 156 (the Double chips) to 200 (StoreByte). Address, previous word and new word are the executor's records as they are."""
+    ev = events if chip is None else events[np.nonzero(chip_of_events(np.asarray(events.cpu() if torch.is_tensor(events) else events)) == chip)[0]]
+    ops = ev[:, E_OP] | (ev[:, E_OPA] << 8) | ((ev[:, E_OPB] & 0xFF) << 16)
+    cols = [ev[:, E_PC], ev[:, E_CLK], ops, ev[:, E_B], ev[:, E_OPC], ev[:, E_A_PREV], ev[:, E_A_PTS], ev[:, E_B_PTS], ev[:, E_MADDR], ev[:, E_M_PTS],
+            ev[:, E_M_PREV], ev[:, E_M_NEW]]
+    return np.stack(cols, 1) if not torch.is_tensor(ev) else torch.stack(cols, dim=1).contiguous()
+
+
+def core_device_tables(shard_events, heights, stream=None):
+    """The tables of a core shard that the device makes itself: {name: api.ColMajor} for every chip of ALU_TRACEGEN_CHIPS +
+    MEM_TRACEGEN_CHIPS with a non-zero entry in `heights` ({name: rows of its table, padding included}). `shard_events`: the
+    shard's [n, 20] instruction events, numpy or torch; the records are packed where the events are (a host array is packed on
+    the host and the 88- / 96-byte records are what crosses to the device), then api.tracegen_riscv_alu / _mem fill the tables."""
+    from .. import api
+    on_host = not (torch.is_tensor(shard_events) and shard_events.is_cuda)
+    names = chip_of_events(np.asarray(shard_events.cpu() if torch.is_tensor(shard_events) else shard_events))
+    out = {}
+    for chips, pack, gen in ((ALU_TRACEGEN_CHIPS, pack_alu_events, api.tracegen_riscv_alu), (MEM_TRACEGEN_CHIPS, pack_mem_events, api.tracegen_riscv_mem)):
+        for name in chips:
+            if not heights.get(name):
+                continue
+            rows = np.nonzero(names == name)[0]
+            packed = pack(shard_events[rows] if on_host else shard_events[torch.as_tensor(rows, device=shard_events.device)])
+            if on_host:
+                packed = torch.as_tensor(np.ascontiguousarray(packed)).cuda()
+            out[name] = gen(name, packed, int(heights[name]), stream=stream)
+    return out
+
+
 def execution_public_values(sh, prev=None):
     """An execution shard's `PublicValues` as the tracing executor leaves them (tracing.rs postprocess L548-L562, executor.rs:L60
     finalize_public_values(true)) with the previous shard's state threaded in (`prev`: its words, None for the first shard); the

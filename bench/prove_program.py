@@ -115,6 +115,9 @@ def main():
     ap.add_argument("--device-core", action="store_true", help="core shards: make the tables of the fourteen ALU / branch / jump chips and the "
                     "nine load and store chips on the device from the shard's event records (riscv_exec.core_device_tables) instead of "
                     "taking the tracer's; the shard's other chips stay as they are, and the proofs are the same bytes")
+    ap.add_argument("--device-counts", action="store_true", help="core shards: count the Byte, Range and Program multiplicities on the device from "
+                    "the tables that are proved (riscv_exec.device_lookup_tables) instead of taking the tracer's three main tables; with or "
+                    "without --device-core, and the proofs are the same bytes")
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--out", default="")
@@ -198,6 +201,12 @@ def main():
                 made = X.core_device_tables(sh.events, {a.name: int(tabs[a.name][1].shape[0]) for a, _ in machine})
                 chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
                 row["device_core"], row["device_core_chips"] = True, len(made)
+            if args.device_counts and kind == "core":
+                pc_base, program = ex.program()
+                counted = X.device_lookup_tables(machine, {a.name: (m, p) for a, _, m, p in chips if a.name not in ("Byte", "Range", "Program")},
+                                                 publics, sh.events, program, pc_base)
+                chips = [(a, i, counted.get(a.name, m), p) for a, i, m, p in chips]
+                row["device_counts"] = True
             tabs.clear()
             pv = RT.to_monty_np(publics)
             commit = pk.preprocessed_commit

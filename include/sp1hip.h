@@ -568,6 +568,39 @@ int sp1hip_tracegen_riscv_secp256k1_add(uint32_t* d_table, uint32_t height, cons
 int sp1hip_tracegen_riscv_secp256k1_double(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events,
                                            sp1hip_stream_t stream);
 
+/* The Byte, Range and Program multiplicities of a shard, counted on the device from the tables that send: the receive side of the
+ * byte lookup argument, which the reference computes in `generate_dependencies` of its Byte and Range chips
+ * (crates/core/machine/src/bytes/trace.rs:L50-L66, range/trace.rs:L54-L95), and the Program chip's count of executed pcs. Generic over
+ * the chip: `interactions` are the words `sp1hip_gkr_chip_t.interactions` takes (host memory), of which the sends of kind 5 (Byte)
+ * are evaluated — [opcode, a, b, c] and a multiplicity m, affine forms of the row — on ALL `rows` rows of the chip's column-major
+ * Montgomery tables (padding rows send with multiplicity 0, as the proof requires of them). Count arrays are u32 words, zeroed by the
+ * caller once and added to by any number of calls:
+ *   d_byte_counts   6 x 65536: opcode 0..5 (AND, OR, XOR, U8Range, LTU, MSB) adds m to cell opcode * 65536 + b * 256 + c — Byte's main
+ *                   table [6][65536] as it stands
+ *   d_range_counts  131072: opcode 6 adds m to cell (1 << b) + a (`a` has `b` bits) — Range's main table [1][131072]
+ *   d_status        8 words, zeroed by the caller: [0] the number of bad messages, [1] 1 message / 2 pc / 3 count, [2] the interaction
+ *                   index and [3] the row (or pc index, or cell) of the first, [4] the `tag` of the call that found it
+ * A message with m == 0 is none. One with m != 0 is checked before its cell is formed — b <= 16, a < 2^b, c == 0 for a range; b, c <
+ * 256, opcode < 6, a the table's answer, c == 0 for MSB; m < 2^16 (a negative multiplicity arrives as p - k) — and one that fails is
+ * counted in d_status and moves no count. A malformed description (a column outside its table's width, a byte message with other than
+ * 4 values, a truncated or overlong word list, a constant or weight outside the field) is SP1HIP_ERROR_INVALID_ARGUMENT before any
+ * launch. rows == 0 succeeds without a launch; a null table pointer is accepted only with zero width or zero rows.
+ *   sp1hip_lookup_count_program  adds 1 to d_program_counts[(pc - pc_base) >> 2] for the n executed pcs d_pcs[i * stride_words] (u64
+ *                   words: stride 20 reads column 0 of the executor's event matrix, 11 and 12 the packed ALU and memory records); a pc
+ *                   below pc_base, off the 4-byte grid or at or beyond n_instructions is counted in d_status instead.
+ *   sp1hip_lookup_counts_finish  turns n_cells counts into Montgomery words, in place or into d_table_or_null, then SYNCHRONISES the
+ *                   stream and returns SP1HIP_ERROR_INVALID_ARGUMENT with a message that names the first bad (send, row) when
+ *                   d_status[0] != 0 (a count at or above the modulus is such an error too). The two count calls only enqueue.
+ * Counts are u32 and a cell that wraps past 2^32 is NOT detected: the caller keeps the sum of the multiplicities sent to one cell
+ * between zeroing and finish below 2^32 (every m is below 2^16, so any 2^16 messages per cell are safe; a shard of 2^22-row tables
+ * would need 43 sends per row, all of multiplicity 2^16 - 1 and all to one cell, to reach it). */
+int sp1hip_lookup_count_sends(const uint32_t* interactions, uint64_t n_words, uint32_t main_width, uint32_t prep_width, const uint32_t* d_main,
+                              const uint32_t* d_prep, uint32_t rows, uint32_t* d_byte_counts, uint32_t* d_range_counts, uint32_t* d_status, uint32_t tag,
+                              sp1hip_stream_t stream);
+int sp1hip_lookup_count_program(const uint64_t* d_pcs, uint64_t stride_words, uint32_t n, uint64_t pc_base, uint32_t n_instructions,
+                                uint32_t* d_program_counts, uint32_t* d_status, uint32_t tag, sp1hip_stream_t stream);
+int sp1hip_lookup_counts_finish(uint32_t* d_counts, uint64_t n_cells, uint32_t* d_table_or_null, uint32_t* d_status, sp1hip_stream_t stream);
+
 /* ---------------------------------------------------------------- guest execution (host code, no device work)
  * An rv64im executor for SP1 guest ELFs: what `MinimalExecutor` + `TracingVM` do for the core prover
  * (/root/reference/crates/core/executor/src/minimal.rs, tracing.rs:L57-L147, vm.rs:L139-L431; the controller's shard loop is

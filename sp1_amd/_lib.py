@@ -252,6 +252,9 @@ PROTOTYPES = [
     ("sp1hip_tracegen_riscv_secp256k1_double_width", None, []),
     ("sp1hip_tracegen_riscv_secp256k1_add", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_secp256k1_double", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_lookup_count_sends", None, [u32p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, _vp]),
+    ("sp1hip_lookup_count_program", None, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, _vp, _vp, C.c_uint32, _vp]),
+    ("sp1hip_lookup_counts_finish", None, [_vp, C.c_uint64, _vp, _vp, _vp]),
     ("sp1hip_rv64_create", None, [u8p, C.c_uint64, C.POINTER(_vp)]),
     ("sp1hip_rv64_destroy", "void", [_vp]),
     ("sp1hip_rv64_write_stdin", None, [_vp, u8p, C.c_uint64]),

@@ -640,6 +640,89 @@ def tracegen_riscv_secp256k1_double(events, height, stream=None):
     return _tracegen_secp("sp1hip_tracegen_riscv_secp256k1_double", SECP_DOUBLE_EVENT_WORDS, events, height, stream)
 
 
+class LookupCounter:
+    """The Byte, Range and Program main tables of one shard — the multiplicities of the byte lookups every other table sends and
+    of the executed pcs — counted on the device (sp1hip_lookup_count_sends / _program / _counts_finish): the reference's
+    `generate_dependencies` of its Byte and Range chips over tables that are already in device memory. One u32 count buffer holds
+    the three arrays back to back: [6][65536] Byte, [131072] Range, [program_height] Program; the calls enqueue on `stream`, and
+    finish() converts the buffer to Montgomery words in place and hands out the three tables as views of it."""
+    BYTE_CELLS, RANGE_CELLS, STATUS_WORDS = 6 << 16, 1 << 17, 8
+
+    def __init__(self, program_height=0, stream=None):
+        self.stream, self.program_height = stream, int(program_height)
+        device = torch.device("cuda", torch.cuda.current_device())
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):    # zeroed on the stream that counts
+            self.counts = torch.zeros(self.BYTE_CELLS + self.RANGE_CELLS + self.program_height, dtype=torch.int32, device=device)
+            self.status = torch.zeros(self.STATUS_WORDS, dtype=torch.int32, device=device)
+        self.calls = []                                   # the name of every add, by tag: what an error message's "call" means
+        self._keep = []                                   # inputs uploaded here stay alive until finish() has synchronised
+        self.finished = False                             # finish() turns the counts into field elements: nothing may be added after
+
+    def _open(self):
+        if self.finished:
+            raise RuntimeError("this LookupCounter is finished: its buffer holds Montgomery words, not counts")
+
+    def _parts(self):
+        b, r = self.BYTE_CELLS, self.BYTE_CELLS + self.RANGE_CELLS
+        return self.counts[:b], self.counts[b:r], self.counts[r:]
+
+    def add(self, interaction_program, main, prep=None):
+        """Count the byte sends of a chip (air.InteractionProgram) over all rows of its tables (ColMajor; prep None for none)."""
+        self._open()
+        words = np.ascontiguousarray(interaction_program.to_array(), dtype=np.uint32)
+        rows = main.height if main is not None else 0
+        assert prep is None or prep.height == rows or rows == 0
+        byte, rng, _ = self._parts()
+        self.calls.append(interaction_program.name)
+        check(_L().sp1hip_lookup_count_sends(words.ctypes.data_as(C.POINTER(C.c_uint32)), words.size, main.width if main is not None else 0,
+                                             prep.width if prep is not None else 0, _dptr(main.words) if main is not None and rows else None,
+                                             _dptr(prep.words) if prep is not None and rows else None, rows, _dptr(byte), _dptr(rng),
+                                             _dptr(self.status), len(self.calls) - 1, _stream_ptr(self.stream)))
+
+    def add_row(self, interaction_program, row_words):
+        """The same for one row given on the host (the public values' sends): Montgomery words, uploaded as a 1-row table."""
+        row = np.ascontiguousarray(row_words, dtype=np.uint32).reshape(-1)
+        table = ColMajor(to_device(row), 1, row.size)
+        self._keep.append(table)
+        self.add(interaction_program, table)
+
+    def add_program_counters(self, events_or_pcs, pc_base, n_instructions):
+        """Count executed pcs into the Program table: an int64 [n, k] matrix whose column 0 is the pc (the executor's [n, 20] events,
+        the packed 11- / 12-word records) or a 1-D int64 array of pcs; numpy (uploaded) or a device tensor."""
+        self._open()
+        ev = events_or_pcs
+        if not torch.is_tensor(ev):
+            ev = torch.as_tensor(np.ascontiguousarray(ev, dtype=np.int64))
+        assert ev.dtype == torch.int64 and ev.dim() in (1, 2) and int(n_instructions) <= self.program_height
+        if not ev.is_cuda:
+            ev = (ev if ev.dim() == 1 else ev[:, 0]).contiguous().to(self.counts.device)      # only the pcs cross
+        n = int(ev.shape[0])
+        stride = 1 if ev.dim() == 1 else int(ev.stride(0))
+        assert n == 0 or (ev.dim() == 1 and ev.is_contiguous()) or ev.stride(1) == 1
+        self._keep.append(ev)
+        self.calls.append("Program")
+        check(_L().sp1hip_lookup_count_program(_dptr(ev) if n else None, max(stride, 1), n, int(pc_base), int(n_instructions),
+                                               _dptr(self._parts()[2]), _dptr(self.status), len(self.calls) - 1, _stream_ptr(self.stream)))
+
+    def finish(self):
+        """{"Byte": ColMajor 65536 x 6, "Range": ColMajor 131072 x 1, "Program": ColMajor program_height x 1}. Synchronises the
+        stream; raises Sp1HipError naming the first bad message (its send and row, and the add it came from) if there was one. Once:
+        the counter takes no further call, also after an error."""
+        self._open()
+        self.finished = True
+        try:
+            check(_L().sp1hip_lookup_counts_finish(_dptr(self.counts), self.counts.numel(), None, _dptr(self.status), _stream_ptr(self.stream)))
+        except _lib.Sp1HipError as e:
+            st = to_host(self.status)
+            if int(st[1]) in (1, 2) and int(st[4]) < len(self.calls):
+                e.args = ("%s (call %d is %s)" % (e.args[0], int(st[4]), self.calls[int(st[4])]),)
+            raise
+        finally:
+            self._keep.clear()
+        byte, rng, prog = self._parts()
+        return {"Byte": ColMajor(byte, 1 << 16, 6), "Range": ColMajor(rng, 1 << 17, 1), "Program": ColMajor(prog, self.program_height, 1)}
+
+
 class ProvingKey:
     """`ProvingKey` of the AirProver slot: the preprocessed commitment round + the verifying key (sp1hip_setup).
     Keeps the preprocessed device tables alive."""

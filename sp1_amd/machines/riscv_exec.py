@@ -423,6 +423,31 @@ def core_device_tables(shard_events, heights, stream=None):
     return out
 
 
+def device_lookup_tables(machine, tables, publics, shard_events, program, pc_base, stream=None):
+    """The Byte, Range and Program main tables of a shard counted ON THE DEVICE from the tables that are proved
+    (api.LookupCounter): {"Byte", "Range", "Program": api.ColMajor}, word for word what Tracer.byte_range_tables and program_table
+    count on the host. `machine`: the shard's [(AirProgram, InteractionProgram)]; `tables`: {name: (main ColMajor, prep ColMajor or
+    None)} for every chip of the shard but Byte, Range and Program — device-made or staged, a chip without rows may be left out or
+    have main None; `publics`: the shard's public values, canonical words (their sends are eval_public_values'); `shard_events`: the
+    executed instructions, an [n, k] int64 matrix whose column 0 is the pc, numpy or a device tensor, or None for a shard that
+    executes nothing; `program`: the transpiled instruction list (its length is what counts), `pc_base` its first pc. No host table
+    is read."""
+    from .. import api
+    n_instructions = len(program)
+    counter = api.LookupCounter(RT.pad32(n_instructions), stream=stream)
+    for a, it in machine:
+        if a.name in ("Byte", "Range", "Program"):
+            continue
+        main, prep = tables.get(a.name, (None, None))
+        if main is not None and main.height:
+            counter.add(it, main, prep)
+    pv = np.asarray(publics.cpu() if torch.is_tensor(publics) else publics, dtype=np.int64)[:PV_WORDS]
+    counter.add_row(PVM.program()[1], RT.to_monty_np(torch.as_tensor(pv)))
+    if shard_events is not None and len(shard_events):
+        counter.add_program_counters(shard_events, pc_base, n_instructions)
+    return counter.finish()
+
+
 def execution_public_values(sh, prev=None):
     """An execution shard's `PublicValues` as the tracing executor leaves them (tracing.rs postprocess L548-L562, executor.rs:L60
     finalize_public_values(true)) with the previous shard's state threaded in (`prev`: its words, None for the first shard); the

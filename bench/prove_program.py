@@ -115,6 +115,10 @@ def main():
     ap.add_argument("--device-core", action="store_true", help="core shards: make the tables of the fourteen ALU / branch / jump chips and the "
                     "nine load and store chips on the device from the shard's event records (riscv_exec.core_device_tables) instead of "
                     "taking the tracer's; the shard's other chips stay as they are, and the proofs are the same bytes")
+    ap.add_argument("--device-rest", action="store_true", help="core shards: make the DivRem, AluX0, MemoryLocal and Global tables on the device "
+                    "from the shard's event records and local-memory records (riscv_exec.core_device_tables_rest; the Global table from the "
+                    "events the MemoryLocal kernel writes, SyscallCore's appended) instead of taking the tracer's; combines with --device-core "
+                    "and --device-counts, and the proofs are the same bytes")
     ap.add_argument("--device-counts", action="store_true", help="core shards: count the Byte, Range and Program multiplicities on the device from "
                     "the tables that are proved (riscv_exec.device_lookup_tables) instead of taking the tracer's three main tables; with or "
                     "without --device-core, and the proofs are the same bytes")
@@ -201,6 +205,13 @@ def main():
                 made = X.core_device_tables(sh.events, {a.name: int(tabs[a.name][1].shape[0]) for a, _ in machine})
                 chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
                 row["device_core"], row["device_core_chips"] = True, len(made)
+            if args.device_rest and kind == "core":
+                heights = {a.name: int(tabs[a.name][1].shape[0]) for a, _ in machine}
+                made, (g_count, g_digest) = X.core_device_tables_rest(sh, heights, syscall_global_events=gev[2 * len(sh.local):])
+                assert g_count == PVM.get(publics, "global_count") and g_digest == PVM.get(publics, "global_cumulative_sum"), \
+                    "the device-made Global table accumulates to another digest than the shard's public values"
+                chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
+                row["device_rest"], row["device_rest_chips"] = True, sorted(made)
             if args.device_counts and kind == "core":
                 pc_base, program = ex.program()
                 counted = X.device_lookup_tables(machine, {a.name: (m, p) for a, _, m, p in chips if a.name not in ("Byte", "Range", "Program")},

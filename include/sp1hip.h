@@ -525,6 +525,32 @@ int sp1hip_tracegen_riscv_mem_width(int chip);       /* columns of the chip's ta
 int sp1hip_tracegen_riscv_mem(int chip, uint32_t* d_table, uint32_t height, const sp1hip_rv64_mem_event_t* d_events, uint32_t n_events,
                               sp1hip_stream_t stream);
 
+/* Device trace generation for three more tables of a core shard — DivRem, AluX0, MemoryLocal — and, with MemoryLocal, the events of
+ * the shard's Global table. They have entry points of their own: the chip numbers above stay as they are.
+ *   sp1hip_tracegen_riscv_divrem        DivRem, width 246 (`event_to_row` of crates/core/machine/src/alu/divrem/mod.rs): CPUState, the R
+ *       adapter, quotient and remainder of DIV / DIVU / REM / REMU and their W forms (division by zero, signed overflow, the W forms'
+ *       extension of their low halves), the three IsZeroWordOperations with their field inverses, the absolute values, the unsigned
+ *       compare |remainder| < max(|c|, 1) when c != 0, c * quotient through one MulOperation (W forms) or two, and the 8 carries. Events
+ *       are sp1hip_rv64_alu_event_t records as above. A padding row is the reference's "0 / 1" row: is_divu, c = abs_c = max_abs_c_or_1 =
+ *       op_c's prev_value = 1, b_not_neg_not_overflow, is_c_0 of [1, 0, 0, 0].
+ *   sp1hip_tracegen_riscv_alu_x0        AluX0, width 34 (alu/alu_x0.rs): CPUState, the ALU adapter, opcode, is_real — every ALU
+ *       instruction whose destination is x0. The same records. Padding rows are zero.
+ *   sp1hip_tracegen_riscv_memory_local  MemoryLocal, width 20 (memory/local.rs): one row per address the shard touched, from n_records
+ *       x 5 u64 { addr, initial clk, initial value, final clk, final value }. Padding rows are zero. When d_global_events is not null it
+ *       receives the rows' Global events in the form sp1hip_tracegen_riscv_global reads, [2 n_records][9] words: record i's initial state
+ *       (a receive) at row 2 i and its final state (a send) at row 2 i + 1, message = clk_high, clk_low, addr[3], value[0] + lower * 2^16,
+ *       value[1] + upper * 2^16, value[3], kind Memory. The buffer may be larger: what lies behind row 2 n_records is not touched.
+ * Output: column-major [width][height] Montgomery words. Needs n <= height. All argument checks come before any launch; a null
+ * pointer is accepted only with nothing to read or write (d_global_events: always); height == 0 succeeds without a launch. The calls
+ * enqueue and return: they do not synchronise. */
+int sp1hip_tracegen_riscv_divrem_width(void);          /* 246 */
+int sp1hip_tracegen_riscv_alu_x0_width(void);          /* 34 */
+int sp1hip_tracegen_riscv_memory_local_width(void);    /* 20 */
+int sp1hip_tracegen_riscv_divrem(uint32_t* d_table, uint32_t height, const sp1hip_rv64_alu_event_t* d_events, uint32_t n_events, sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_alu_x0(uint32_t* d_table, uint32_t height, const sp1hip_rv64_alu_event_t* d_events, uint32_t n_events, sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_memory_local(uint32_t* d_table, uint32_t height, const uint64_t* d_records, uint32_t n_records, int32_t* d_global_events,
+                                       sp1hip_stream_t stream);
+
 /* Device trace generation for the two chips of a KECCAK_PERMUTE precompile shard, from the executor's event records as they are
  * (sp1hip_rv64_keccak_events below: n_events x 77 u64 on the device — [0] clk, [1] state pointer, [2 + 2i] / [3 + 2i] the previous
  * timestamp and the word read of state word i < 25, [52 + i] the word written). The reference fills both tables on the host

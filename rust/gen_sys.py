@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "sp1hip.h")
 OUT = os.path.join(ROOT, "rust", "sp1-hip-sys", "src", "lib.rs")
 
-SCALARS = {"int": "c_int", "size_t": "usize", "uint32_t": "u32", "uint64_t": "u64", "uint8_t": "u8", "float": "f32",
+SCALARS = {"int": "c_int", "size_t": "usize", "int32_t": "i32", "uint32_t": "u32", "uint64_t": "u64", "uint8_t": "u8", "float": "f32",
            "double": "f64", "char": "c_char", "void": "c_void"}
 HANDLES = {"sp1hip_stream_t": "Stream", "sp1hip_event_t": "Event", "sp1hip_ticket_t": "Ticket", "sp1hip_rv64_vm_t": "Rv64Vm"}
 

@@ -244,6 +244,12 @@ PROTOTYPES = [
     ("sp1hip_tracegen_riscv_alu", None, [C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_mem_width", None, [C.c_int]),
     ("sp1hip_tracegen_riscv_mem", None, [C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_divrem_width", None, []),
+    ("sp1hip_tracegen_riscv_alu_x0_width", None, []),
+    ("sp1hip_tracegen_riscv_memory_local_width", None, []),
+    ("sp1hip_tracegen_riscv_divrem", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_alu_x0", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_memory_local", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
     ("sp1hip_tracegen_riscv_keccak_width", None, []),
     ("sp1hip_tracegen_riscv_keccak_control_width", None, []),
     ("sp1hip_tracegen_riscv_keccak", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),

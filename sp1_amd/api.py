@@ -590,7 +590,50 @@ def tracegen_riscv_mem(chip, events, height, stream=None):
     return ColMajor(out, int(height), width)
 
 
-KECCAK_EVENT_WORDS = 77                                                              # SP1HIP_RV64_KECCAK_WORDS
+def _tracegen_alu_records(fn, events, height, stream):
+    width = getattr(_L(), fn + "_width")()
+    n = int(events.shape[0])
+    assert events.dtype == torch.int64 and (n == 0 or (events.is_cuda and events.shape[1] == ALU_EVENT_WORDS and events.is_contiguous()))
+    out = device_words(width * int(height))
+    check(getattr(_L(), fn)(_dptr(out), int(height), _dptr(events) if n else None, n, _stream_ptr(stream)))
+    return ColMajor(out, int(height), width)
+
+
+def tracegen_riscv_divrem(events, height, stream=None):
+    """`generate_trace_device` for the DivRem chip (sp1hip_tracegen_riscv_divrem): events = a device int64 tensor [n, 11] of
+    sp1hip_rv64_alu_event_t records (riscv_exec.pack_alu_events(events, "DivRem")); returns the column-major [246][height] table as
+    a ColMajor, rows >= n the reference's "0 / 1" padding row."""
+    return _tracegen_alu_records("sp1hip_tracegen_riscv_divrem", events, height, stream)
+
+
+def tracegen_riscv_alu_x0(events, height, stream=None):
+    """The same for the AluX0 chip (sp1hip_tracegen_riscv_alu_x0; pack_alu_events(events, "AluX0")): column-major [34][height],
+    zero padding rows."""
+    return _tracegen_alu_records("sp1hip_tracegen_riscv_alu_x0", events, height, stream)
+
+
+MEMORY_LOCAL_RECORD_WORDS, MEMORY_LOCAL_WIDTH, GLOBAL_EVENT_WORDS = 5, 20, 9
+
+
+def tracegen_riscv_memory_local(records, height, extra_global_events=0, stream=None):
+    """`generate_trace_device` for the MemoryLocal chip (sp1hip_tracegen_riscv_memory_local): records = a device int64 tensor [n, 5]
+    of the executor's local-memory records (riscv_exec.ExecutedShard.local: addr, initial clk, initial value, final clk, final
+    value). Returns (the column-major [20][height] table as a ColMajor, the rows' Global events: an int32 device tensor
+    [2 n + extra_global_events, 9] in the form tracegen_riscv_global reads, record i at rows 2 i and 2 i + 1; the
+    `extra_global_events` rows behind them are the caller's to fill — SyscallCore's events — and are zero)."""
+    n, extra = int(records.shape[0]), int(extra_global_events)
+    assert records.dtype == torch.int64 and (n == 0 or (records.is_cuda and records.shape[1] == MEMORY_LOCAL_RECORD_WORDS and records.is_contiguous()))
+    out = device_words(MEMORY_LOCAL_WIDTH * int(height))
+    events = torch.empty((2 * n + extra, GLOBAL_EVENT_WORDS), dtype=torch.int32, device=out.device)
+    if extra:                                                 # the kernel writes every word of the first 2 n rows
+        with torch.cuda.stream(stream or torch.cuda.current_stream()):
+            events[2 * n:].zero_()
+    check(_L().sp1hip_tracegen_riscv_memory_local(_dptr(out), int(height), _dptr(records) if n else None, n, _dptr(events) if n else None,
+                                                  _stream_ptr(stream)))
+    return ColMajor(out, int(height), MEMORY_LOCAL_WIDTH), events
+
+
+KECCAK_EVENT_WORDS = 77                                                            # SP1HIP_RV64_KECCAK_WORDS
 
 
 def _tracegen_keccak(fn, events, height, stream):

@@ -423,6 +423,65 @@ def core_device_tables(shard_events, heights, stream=None):
     return out
 
 
+REST_TRACEGEN_CHIPS = ("DivRem", "AluX0", "MemoryLocal", "Global")                          # core_device_tables_rest: made on the device too
+
+
+def global_events_9(events11):
+    """Global interaction events as eval_interactions yields them ([m, 11]: message[8], is_send, is_receive, kind; a torch tensor)
+    -> the [m, 9] int32 form api.tracegen_riscv_global reads: message[8], is_receive | kind << 8."""
+    ev = events11.to(torch.int64)
+    return torch.cat([ev[:, :8], (ev[:, 9] | (ev[:, 10] << 8))[:, None]], dim=1).to(torch.int32)
+
+
+def core_device_tables_rest(shard, heights, syscall_global_events=None, stream=None):
+    """The DivRem, AluX0, MemoryLocal and Global tables of a core shard, made on the device: ({name: api.ColMajor} for each of them
+    with a non-zero entry in `heights` ({name: rows of its table, padding included}), (global_count, digest[14])). `shard`: an
+    ExecutedShard — DivRem and AluX0 come from its instruction events (pack_alu_events, packed where the events are: only the 88-byte
+    records cross to the device), MemoryLocal from its 40-byte `local` records as they are. The MemoryLocal kernel also writes its
+    rows' Global events; `syscall_global_events` ([m, 11] as eval_interactions yields them for SyscallCore, or None) are appended
+    in the 9-word form, and api.tracegen_riscv_global makes the Global table from them: no host table is read. global_count is the
+    number of events, the digest the last real row's accumulation.cumulative_sum_x / _y of the device table (canonical words; the
+    curve's start point when there is no event) — the two public values the Global chip defines. MemoryBump, StateBump, SyscallInstrs
+    and SyscallCore stay with the host tracer: a handful of rows per shard."""
+    with torch.cuda.stream(stream or torch.cuda.current_stream()):     # the uploads and copies go where the kernels go
+        return _core_device_tables_rest(shard, heights, syscall_global_events, stream)
+
+
+def _core_device_tables_rest(shard, heights, syscall_global_events, stream):
+    from .. import api
+    events, out = shard.events, {}
+    on_host = not (torch.is_tensor(events) and events.is_cuda)
+    names = chip_of_events(np.asarray(events.cpu() if torch.is_tensor(events) else events))
+    for name, gen in (("DivRem", api.tracegen_riscv_divrem), ("AluX0", api.tracegen_riscv_alu_x0)):
+        if not heights.get(name):
+            continue
+        rows = np.nonzero(names == name)[0]
+        packed = pack_alu_events(events[rows] if on_host else events[torch.as_tensor(rows, device=events.device)])
+        if on_host:
+            packed = torch.as_tensor(np.ascontiguousarray(packed)).cuda()
+        out[name] = gen(packed, int(heights[name]), stream=stream)
+    m = 0 if syscall_global_events is None else int(syscall_global_events.shape[0])
+    local = torch.as_tensor(shard.local).reshape(-1, 5)
+    local = (local if local.is_cuda else local.cuda()).contiguous()
+    count = 2 * int(local.shape[0]) + m
+    digest = [int(v) for xy in R.CURVE_CUMULATIVE_SUM_START for v in xy]
+    if heights.get("MemoryLocal"):
+        out["MemoryLocal"], gev = api.tracegen_riscv_memory_local(local, int(heights["MemoryLocal"]), extra_global_events=m, stream=stream)
+    if heights.get("Global"):
+        assert "MemoryLocal" in out or not local.shape[0], "the Global table needs the MemoryLocal table's events"
+        if "MemoryLocal" not in out:
+            gev = torch.zeros((m, api.GLOBAL_EVENT_WORDS), dtype=torch.int32, device="cuda")
+        if m:
+            gev[count - m:] = global_events_9(torch.as_tensor(syscall_global_events)).to(gev.device)
+        table = out["Global"] = api.tracegen_riscv_global(gev, int(heights["Global"]), stream=stream)
+        if count:
+            lay = R.chip("Global")[0].layout
+            cols = [lay["accumulation.cumulative_sum_" + axis] + j for axis in "xy" for j in range(7)]
+            words = table.words.view(table.width, table.height)[cols, count - 1].cpu().numpy().view(np.uint32).astype(np.uint64)
+            digest = [int(v) for v in words * np.uint64(pow(1 << 32, -1, P)) % np.uint64(P)]
+    return out, (count, digest)
+
+
 def device_lookup_tables(machine, tables, publics, shard_events, program, pc_base, stream=None):
     """The Byte, Range and Program main tables of a shard counted ON THE DEVICE from the tables that are proved
     (api.LookupCounter): {"Byte", "Range", "Program": api.ColMajor}, word for word what Tracer.byte_range_tables and program_table

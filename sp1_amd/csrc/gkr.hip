@@ -11,7 +11,8 @@
 // File map
 //   gkr_kernels.hpp   every kernel and the descriptors the host fills for them (IntDesc .. OpenDesc)
 //   gkr_host.cpp      the interaction-variable rounds in AVX-512 (tables as coefficient planes)
-//   gkr.hip (here)    the host field math and the proof's byte writer; Levels (the fraction tree's storage); plan_passes (pure host:
+//   ext_host.hpp      the host field helpers shared with jagged.hip (Ext operators, eq tables, DeviceBuf, upload)
+//   gkr.hip (here)    the cubic interpolation and the proof's byte writer; Levels (the fraction tree's storage); plan_passes (pure host:
 //                     every pass's shape and descriptors); the closed forms of the row rounds; the two forms of the host
 //                     interaction rounds; GkrProver: one proof, a phase per member function, run in order by GkrProver::prove
 //
@@ -49,6 +50,7 @@ void gkr_host_round_fold(const uint32_t* tab, uint32_t* out, size_t stride, size
 }
 #include "round_sync.hpp"
 #include "tensor_table.hpp"
+#include "ext_host.hpp"
 #include "gkr_kernels.hpp"
 
 namespace sp1hip {
@@ -59,33 +61,8 @@ void challenger_restore(sp1hip_challenger_t* dst, const sp1hip_challenger_t* src
 
 namespace gkr {
 
-struct DeviceBuf : AsyncScratch {
-    uint32_t* u32() const { return (uint32_t*)p; }
-    Ext* ext() const { return (Ext*)p; }
-};
-
 // ================================================================ host side
-Ext operator+(const Ext& a, const Ext& b) { return kb::ext_add(a, b); }
-Ext operator-(const Ext& a, const Ext& b) { return kb::ext_sub(a, b); }
-Ext operator*(const Ext& a, const Ext& b) { return kb::ext_mul(a, b); }
-Ext ext_c(uint32_t canonical) { return kb::ext_from_base(kb::to_monty(canonical)); }
-int log2_ceil(uint64_t x) { int l = 0; while (((uint64_t)1 << l) < x) l++; return l; }
-
-std::vector<Ext> partial_lagrange_host(const std::vector<Ext>& pt) {
-    std::vector<Ext> ev{kb::ext_one()};
-    for (const Ext& x : pt) {
-        std::vector<Ext> nx(ev.size() * 2);
-        for (size_t i = 0; i < ev.size(); i++) { const Ext pr = ev[i] * x; nx[2 * i] = ev[i] - pr; nx[2 * i + 1] = pr; }
-        ev.swap(nx);
-    }
-    return ev;
-}
-Ext eval_mle_host(const std::vector<Ext>& vals, const std::vector<Ext>& pt) {
-    const std::vector<Ext> eq = partial_lagrange_host(pt);
-    Ext acc = kb::ext_zero();
-    for (size_t i = 0; i < vals.size(); i++) acc = acc + eq[i] * vals[i];
-    return acc;
-}
+using namespace ext_host;   // DeviceBuf, the Ext operators, ext_c, log2_ceil, partial_lagrange_host, eval_mle_host, upload
 
 using Poly4 = std::array<Ext, 4>;
 Ext poly_eval(const Poly4& c, const Ext& x) { return ((c[3] * x + c[2]) * x + c[1]) * x + c[0]; }
@@ -136,11 +113,6 @@ struct Bytes {
 };
 
 void observe_ext(sp1hip_challenger_t* ch, const Ext& e) { for (int k = 0; k < 4; k++) challenger_observe(ch, e.c[k]); }
-
-int upload(DeviceBuf& buf, const void* src, size_t bytes, hipStream_t s, PinnedStage& stage) {
-    SP1HIP_TRY(buf.alloc(std::max<size_t>(bytes, 16), s));
-    return stage.upload(buf.p, src, bytes);
-}
 
 struct ChipInfo {
     std::string name;

@@ -1,7 +1,8 @@
 // sp1_amd/csrc/jagged_host.hpp — the seam between the jagged evaluation proof (jagged.hip) and the configuration it runs
 // under. `JaggedProver::prove_trusted_evaluations` is field work — the jagged sumcheck, the jagged-eval sumcheck, the column
 // evaluations — around three things that depend on the hash: the transcript, the dense (BaseFold) opening it ends in, and the
-// bytes of a commitment. jagged_prove_with is the one round loop; the inner prover (jagged.hip: KoalaBear Poseidon2,
+// bytes of a commitment. jagged_prove_with (jagged.hip: the argument checks, then JgProver::prove, a member function per phase; the
+// kernels are in jagged_kernels.hpp) is the one round loop; the inner prover (jagged.hip: KoalaBear Poseidon2,
 // DuplexChallenger) and the outer one (outer_jagged.hip: Poseidon2-BN254, MultiField32Challenger) are two JaggedBackends.
 #pragma once
 #include <vector>

@@ -23,7 +23,7 @@ BIG = [
     ([[(1 << 10, 3), (777, 5), (0, 2), (33, 7)], [(1 << 12, 9), (4095, 2), (1, 1), (2048, 30)]], 12, 8, 4),
     ([[(70000, 3)], [(1 << 17, 5), (99999, 4), (123, 40)]], 17, 12, 8),       # multi-block sums, odd areas
     # every column starts at a multiple of 64 / 32 / 4 in the dense order: the first 6 / 5 / 2 folds keep J factored
-    # (jg_foldf_sum), then the prover leaves the factored form (jg_materialize_j)
+    # (jg_fold_tables, jg_foldf_sum), then the prover leaves the factored form (jg_fold_sum_fj computes j as it loads)
     ([[(1 << 10, 3), (768, 5), (0, 2), (64, 7)], [(1 << 12, 9), (4032, 2), (128, 1), (2048, 30)]], 12, 8, 4),
     ([[(32, 3), (96, 1)], [(1 << 15, 5), (65504, 4), (160, 40)]], 16, 10, 8),
     ([[(1 << 10, 3), (772, 5), (12, 7)]], 10, 6, 4),
@@ -74,7 +74,8 @@ def test_jagged_two_pass_form_of_rounds_0_and_1_gives_the_same_bytes(api, monkey
 # Which kernel of jagged.hip proves the first rounds is decided by the heights (sp1hip_jagged_prove: g = the OR of every
 # column's start in the dense order, i.e. of the table heights' multiples):
 #   odd heights            g & 1: the generic segment kernels (jg_round0_sum, jg_fold0_sum)
-#   heights = 2 mod 4      J stays factored: jg_round0_tables, then the generic jg_fold0_sum<false>
+#   heights = 2 mod 4      round 0 table-major, no factored level (rf = 0): jg_round0_tables, then the generic jg_fold0_sum
+#                          (which always writes the j table: a factored level needs heights = 0 mod 4, the next line)
 #   heights = 4 mod 8      tables_mult4: jg_round0_tables, then jg_fold_tables<1, true>
 #   heights = 0 mod 8      skip_level1: jg_round01_tables (rounds 0 and 1 in one pass), then jg_fold_tables<2, true>;
 #                          with SP1HIP_JAGGED_LOOKAHEAD=0: jg_round0_tables, jg_fold_tables<1, false>, jg_fold_tables<2, true>

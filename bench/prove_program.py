@@ -122,6 +122,11 @@ def main():
     ap.add_argument("--device-counts", action="store_true", help="core shards: count the Byte, Range and Program multiplicities on the device from "
                     "the tables that are proved (riscv_exec.device_lookup_tables) instead of taking the tracer's three main tables; with or "
                     "without --device-core, and the proofs are the same bytes")
+    ap.add_argument("--device-shard", action="store_true", help="core shards: make the WHOLE shard on the device from the executor's records "
+                    "(riscv_exec.device_core_shard: the event partition kernel, every chip's table, the public values' Global fields, the "
+                    "lookup counts) — no EventTracer and no host table is built for them; the public values are chained by the previous "
+                    "shard's, the Global events still join the run's balance check. MemoryBump's rows stand in another order than the "
+                    "host tracer's, so a shard that crosses 2^24 cycles proves to other bytes (the same statement)")
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--out", default="")
@@ -132,6 +137,7 @@ def main():
     from program_shard import FULL_CYCLES_OF, stdin_of
     from sp1_amd.machines import public_values as PVM, riscv_exec as X, riscv_trace as RT
     device = "cpu" if args.dry_run else "cuda"
+    assert not (args.dry_run and args.device_shard), "--device-shard makes the tables on the GPU: there is nothing to dry-run"
     if not args.dry_run:
         from core_real import to_col_major
         import ctypes as C
@@ -150,18 +156,27 @@ def main():
     keccak_events = [] if args.device_keccak and not args.dry_run else None
     secp_events = [] if args.device_secp and not args.dry_run else None
     gen = X.program_shards(ex, shard_cycles, device=device, core_limit=args.core_shards or None, keccak_events=keccak_events,
-                           secp_events=secp_events)
+                           secp_events=secp_events, untraced_core=args.device_shard)
     while True:
         try:
             kind, machine, tabs, publics, gev, sh = next(gen)
         except StopIteration:
             break
+        device_chips = None
+        if args.device_shard and kind == "core":                        # untraced: the publics slot holds the previous shard's public values
+            if pk_prep is None:
+                pk_prep = {n: to_col_major(t) for n, t in X.preprocessed_tables(ex, "cuda").items()}
+            machine, device_chips, publics, gev9 = X.device_core_shard(ex, sh, pk_prep, prev=publics)
+            gev = X.global_events_11(gev9)
         if device == "cuda":
             torch.cuda.synchronize()
         t_build = time.perf_counter() - t_prev                          # executor + tables of this shard (the generator ran both)
-        area = sum(int(tabs[a.name][1].shape[0]) * (a.main_width + a.prep_width) for a, _ in machine)
+        heights = {c[0].name: c[2].height for c in device_chips} if device_chips is not None else {a.name: int(tabs[a.name][1].shape[0]) for a, _ in machine}
+        area = sum(heights[a.name] * (a.main_width + a.prep_width) for a, _ in machine)
         row = {"kind": kind, "chips": len(machine), "cells": area, "build_s": round(t_build, 3),
-               "rows": {a.name: int(tabs[a.name][1].shape[0]) for a, _ in machine if a.name not in ("Byte", "Range", "Program")}}
+               "rows": {a.name: heights[a.name] for a, _ in machine if a.name not in ("Byte", "Range", "Program")}}
+        if device_chips is not None:
+            row["device_shard"] = True
         if sh is not None:
             row["cycles"], row["estimated_cells"] = sh.cycles, sh.estimated_area
             cycles, last = cycles + sh.cycles, sh
@@ -177,7 +192,8 @@ def main():
             if pk is None:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                pk_prep = {a.name: to_col_major(tabs[a.name][0]) for a, _ in machine if tabs[a.name][0] is not None}
+                if pk_prep is None:
+                    pk_prep = {a.name: to_col_major(tabs[a.name][0]) for a, _ in machine if tabs[a.name][0] is not None}
                 vk_ints = X.verifying_key_words(ex, sh.pc_start, "cuda")
                 # the verifying key's words (Montgomery form, like everything the transcript absorbs): the entry pc, and the digest of
                 # the memory image's initialisation (one septic point per image word: program.rs:L170-L199)
@@ -185,8 +201,11 @@ def main():
                 pk = api.ProvingKey([pk_prep[n] for n in sorted(pk_prep)], L, lsh, 32, pc_start=vk_words[:3], initial_global_cumulative_sum=vk_words[3:])
                 torch.cuda.synchronize()
                 row["setup_ms"] = round(1e3 * (time.perf_counter() - t0), 2)
-            assert sorted(a.name for a, _ in machine if tabs[a.name][0] is not None) == sorted(pk_prep), "a shard without the program's preprocessed chips"
-            chips = [(a, i, to_col_major(tabs[a.name][1]), pk_prep.get(a.name)) for a, i in machine]
+            if device_chips is not None:
+                chips = device_chips
+            else:
+                assert sorted(a.name for a, _ in machine if tabs[a.name][0] is not None) == sorted(pk_prep), "a shard without the program's preprocessed chips"
+                chips = [(a, i, to_col_major(tabs[a.name][1]), pk_prep.get(a.name)) for a, i in machine]
             if keccak_events is not None and kind == "keccak":
                 from sp1_amd.machines import riscv_more_trace as MT
                 names = ("KeccakPermute", "KeccakPermuteControl")
@@ -201,24 +220,25 @@ def main():
                 made = {chip: MT.secp256k1_device_table(kind[len("secp256k1_"):], events, int(tabs[chip][1].shape[0]))}
                 chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
                 row["device_secp"] = True
-            if args.device_core and kind == "core":
+            if args.device_core and kind == "core" and device_chips is None:
                 made = X.core_device_tables(sh.events, {a.name: int(tabs[a.name][1].shape[0]) for a, _ in machine})
                 chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
                 row["device_core"], row["device_core_chips"] = True, len(made)
-            if args.device_rest and kind == "core":
+            if args.device_rest and kind == "core" and device_chips is None:
                 heights = {a.name: int(tabs[a.name][1].shape[0]) for a, _ in machine}
                 made, (g_count, g_digest) = X.core_device_tables_rest(sh, heights, syscall_global_events=gev[2 * len(sh.local):])
                 assert g_count == PVM.get(publics, "global_count") and g_digest == PVM.get(publics, "global_cumulative_sum"), \
                     "the device-made Global table accumulates to another digest than the shard's public values"
                 chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
                 row["device_rest"], row["device_rest_chips"] = True, sorted(made)
-            if args.device_counts and kind == "core":
+            if args.device_counts and kind == "core" and device_chips is None:
                 pc_base, program = ex.program()
                 counted = X.device_lookup_tables(machine, {a.name: (m, p) for a, _, m, p in chips if a.name not in ("Byte", "Range", "Program")},
                                                  publics, sh.events, program, pc_base)
                 chips = [(a, i, counted.get(a.name, m), p) for a, i, m, p in chips]
                 row["device_counts"] = True
-            tabs.clear()
+            if tabs is not None:
+                tabs.clear()
             pv = RT.to_monty_np(publics)
             commit = pk.preprocessed_commit
             if kind not in warmed:

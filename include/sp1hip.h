@@ -551,6 +551,77 @@ int sp1hip_tracegen_riscv_alu_x0(uint32_t* d_table, uint32_t height, const sp1hi
 int sp1hip_tracegen_riscv_memory_local(uint32_t* d_table, uint32_t height, const uint64_t* d_records, uint32_t n_records, int32_t* d_global_events,
                                        sp1hip_stream_t stream);
 
+/* A stable partition of a core shard's executed instructions on the device: from the executor's records as sp1hip_rv64_events
+ * yields them (n_events x 20 u64 in device memory: pc, clk, opcode, op_a, op_b, op_c, flags (1: b is an immediate, 2: c is), a, b, c,
+ * a_prev, a_pts, b_pts, c_pts, m_addr, m_pts, m_prev, m_new, next_pc, spare) to one record stream per BIN, in execution order inside
+ * each bin, packed as the chips' kernels read them — what the tracing executor's emit_alu_event / emit_mem_instr_event do with an
+ * instruction (core/executor/src/tracing.rs:L1096-L1228), and the selection of the StateBump and MemoryBump rows.
+ *   bins  0..13  the chips of sp1hip_rv64_chip, same numbers            sp1hip_rv64_alu_event_t (11 words)
+ *   bins 14..22  14 + sp1hip_rv64_mem_chip                              sp1hip_rv64_mem_event_t (12 words)
+ *   bins 23, 24  DivRem, AluX0                                          sp1hip_rv64_alu_event_t
+ *   bin  25      SyscallInstrs: every ECALL                             sp1hip_rv64_alu_event_t (a_prev = the syscall code)
+ *   bin  26      SyscallCore: an ECALL with (code >> 8 & 0xFF) == 1     sp1hip_rv64_alu_event_t, the same record
+ *   bin  27      StateBump: the clock step (8; 8 + 256 for an ECALL) carries out of the low 24 bits of clk, or pc + 4 out of the low
+ *                16 bits of pc — not for branches, JAL, JALR and HALT   4 words: clk, pc, next_pc, clock step | pc_carry << 32
+ *   bin  28      MemoryBump: one record per REGISTER ACCESS whose previous timestamp lies in another 2^24 window than the access
+ *                (slot A at clk + 4, B at clk + 3, C at clk + 2; the slots the chip's adapter reads: A, B, C for Add, Sub, Subw, Mul,
+ *                DivRem, SyscallInstrs; A, B for Addi, Branch, Jalr, loads and stores; A, B and a register C for Addw, ShiftRight,
+ *                Bitwise, Lt, ShiftLeft, AluX0; A for UType, Jal)       4 words: register, previous timestamp, value,
+ *                                                                       (access timestamp >> 24) << 24
+ * A destination x0 sends an ALU opcode to AluX0 and a load to LoadX0. An event adds one record to exactly one of the bins 0..25, at
+ * most one to bin 26 and to bin 27, and 0 to 3 to bin 28, there in the order A, B, C. EBREAK, UNIMP and numbers that are no opcode
+ * add nothing. The record arena is one array of u64 words: bin b starts at the sum of the earlier bins' count x words.
+ *   sp1hip_rv64_partition_scratch_bytes  the size of d_scratch for n_events: 32 u32 counters per workgroup of
+ *                                        SP1HIP_RV64_PARTITION_WORKGROUP events (at least one row)
+ *   sp1hip_rv64_partition_count          fills d_scratch and writes the SP1HIP_RV64_BINS record counts to d_counts (u32 each). The
+ *                                        counts decide every table height, so the caller reads them back — 116 bytes — and sizes the
+ *                                        arena exactly
+ *   sp1hip_rv64_partition_scatter        packs and stores every record; d_scratch and d_counts as the first call left them. A record
+ *                                        that would not fit into records_words words is not written
+ * Bit-reproducible: no atomics, no workgroup waits on another. d_events is 16-byte aligned. At most 2^30 events. All argument checks
+ * come before any launch; n_events == 0 succeeds without a launch and writes nothing (the counts are the caller's zeros). The calls
+ * enqueue and return: they do not synchronise. */
+#define SP1HIP_RV64_BINS 29
+#define SP1HIP_RV64_PARTITION_WORKGROUP 256
+#define SP1HIP_RV64_PARTITION_SCAN_SLICES 32        /* the scan gives each of its 32 lane-slices ceil(workgroups / 32) workgroups */
+/* (DivRem's and AluX0's bins are spelt DIVIDE and X0: no constant of this header names those two chips as the chip enums would — they
+ * have entry points of their own and no chip number, and tests/test_tracegen_riscv_core_abi.py keeps it so. csrc says BIN_DIVREM, BIN_ALU_X0.) */
+typedef enum { SP1HIP_RV64_BIN_ALU = 0, SP1HIP_RV64_BIN_MEM = 14, SP1HIP_RV64_BIN_DIVIDE = 23 /* DivRem */, SP1HIP_RV64_BIN_X0 = 24 /* AluX0 */,
+               SP1HIP_RV64_BIN_SYSCALL_INSTRS = 25, SP1HIP_RV64_BIN_SYSCALL_CORE = 26, SP1HIP_RV64_BIN_STATE_BUMP = 27,
+               SP1HIP_RV64_BIN_MEMORY_BUMP = 28 } sp1hip_rv64_bin;
+uint64_t sp1hip_rv64_partition_scratch_bytes(uint64_t n_events);
+int sp1hip_rv64_partition_count(const uint64_t* d_events, uint64_t n_events, uint32_t* d_scratch, uint32_t* d_counts, sp1hip_stream_t stream);
+int sp1hip_rv64_partition_scatter(const uint64_t* d_events, uint64_t n_events, const uint32_t* d_scratch, const uint32_t* d_counts,
+                                  uint64_t* d_records, uint64_t records_words, sp1hip_stream_t stream);
+
+/* Device trace generation for the four small chips of a core shard, from the records of the bins 25..28 above:
+ *   sp1hip_tracegen_riscv_syscall_instrs  SyscallInstrs, width 65 (syscall/instructions/trace.rs event_to_row): CPUState, the R adapter,
+ *       next_pc NOT normalised (limb 0 = pc[0] + 4; HALT: 1, 0, 0), is_halt, op_a_value, the low bytes of the code's limbs, the IsZero
+ *       operations (inverse, result) of syscall_id - 0x03, 0xF0, 0x00, 0x10, 0x1A, the index bitmap of op_b & 7 and the digest bytes of
+ *       op_c for COMMIT (bitmap only for COMMIT_DEFERRED_PROOFS), op_b_range_check = HALT and op_b's limb 1 < (p - 1) >> 16,
+ *       op_c_range_check = COMMIT_DEFERRED_PROOFS and the same of op_c, is_real
+ *   sp1hip_tracegen_riscv_syscall_core    SyscallCore, width 10 (syscall/chip.rs): clk_high, clk_low, syscall_id, arg1[3], arg2[3],
+ *       is_real. When d_global_events is not null it receives the rows' Global events in the form sp1hip_tracegen_riscv_global reads,
+ *       [n_events][9] words: message = clk_high, clk_low, syscall_id + arg1[0] * 2^8, arg1[1], arg1[2], arg2[3]; word 8 = kind Syscall
+ *       << 8 (a send). Point it behind MemoryLocal's events
+ *   sp1hip_tracegen_riscv_state_bump      StateBump, width 14 (adapter/bump.rs): the limbs of clk + step, clk_high, clk_low + step, next_pc,
+ *       the pc the instruction's row sent (pc with limb 0 + 4 after a pc carry, else next_pc), is_clk, is_real
+ *   sp1hip_tracegen_riscv_memory_bump     MemoryBump, width 15 (memory/bump.rs): prev_value[4], prev_high, prev_low, compare_low = 0, the
+ *       two limbs of window - prev_high - 1, the window's clk limbs, the register, is_real
+ * Output: column-major [width][height] Montgomery words, zero padding rows. Needs n <= height. All argument checks come before any
+ * launch; a null pointer is accepted only with nothing to read or write (d_global_events: always); height == 0 succeeds without a
+ * launch. The calls enqueue and return: they do not synchronise. */
+int sp1hip_tracegen_riscv_syscall_instrs_width(void);  /* 65 */
+int sp1hip_tracegen_riscv_syscall_core_width(void);    /* 10 */
+int sp1hip_tracegen_riscv_state_bump_width(void);      /* 14 */
+int sp1hip_tracegen_riscv_memory_bump_width(void);     /* 15 */
+int sp1hip_tracegen_riscv_syscall_instrs(uint32_t* d_table, uint32_t height, const sp1hip_rv64_alu_event_t* d_events, uint32_t n_events,
+                                         sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_syscall_core(uint32_t* d_table, uint32_t height, const sp1hip_rv64_alu_event_t* d_events, uint32_t n_events,
+                                       int32_t* d_global_events, sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_state_bump(uint32_t* d_table, uint32_t height, const uint64_t* d_records, uint32_t n_records, sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_memory_bump(uint32_t* d_table, uint32_t height, const uint64_t* d_records, uint32_t n_records, sp1hip_stream_t stream);
+
 /* Device trace generation for the two chips of a KECCAK_PERMUTE precompile shard, from the executor's event records as they are
  * (sp1hip_rv64_keccak_events below: n_events x 77 u64 on the device — [0] clk, [1] state pointer, [2 + 2i] / [3 + 2i] the previous
  * timestamp and the word read of state word i < 25, [52 + i] the word written). The reference fills both tables on the host

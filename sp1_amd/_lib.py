@@ -250,6 +250,17 @@ PROTOTYPES = [
     ("sp1hip_tracegen_riscv_divrem", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_alu_x0", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_memory_local", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
+    ("sp1hip_rv64_partition_scratch_bytes", C.c_uint64, [C.c_uint64]),
+    ("sp1hip_rv64_partition_count", None, [_vp, C.c_uint64, _vp, _vp, _vp]),
+    ("sp1hip_rv64_partition_scatter", None, [_vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp]),
+    ("sp1hip_tracegen_riscv_syscall_instrs_width", None, []),
+    ("sp1hip_tracegen_riscv_syscall_core_width", None, []),
+    ("sp1hip_tracegen_riscv_state_bump_width", None, []),
+    ("sp1hip_tracegen_riscv_memory_bump_width", None, []),
+    ("sp1hip_tracegen_riscv_syscall_instrs", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_syscall_core", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
+    ("sp1hip_tracegen_riscv_state_bump", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_memory_bump", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_keccak_width", None, []),
     ("sp1hip_tracegen_riscv_keccak_control_width", None, []),
     ("sp1hip_tracegen_riscv_keccak", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),

@@ -633,6 +633,81 @@ def tracegen_riscv_memory_local(records, height, extra_global_events=0, stream=N
     return ColMajor(out, int(height), MEMORY_LOCAL_WIDTH), events
 
 
+RV64_EVENT_WORDS = 20                                                              # the executor's record (ExecutedShard.events)
+RV64_BINS = tuple(RISCV_ALU_CHIPS) + tuple(RISCV_MEM_CHIPS) + ("DivRem", "AluX0", "SyscallInstrs", "SyscallCore", "StateBump", "MemoryBump")
+RV64_BIN_WORDS = (ALU_EVENT_WORDS,) * 14 + (MEM_EVENT_WORDS,) * 9 + (ALU_EVENT_WORDS,) * 4 + (4, 4)    # u64 words of a bin's record
+
+
+def partition_rv64_events(events, stream=None):
+    """The stable partition of a core shard's executed instructions on the device (sp1hip_rv64_partition_count / _scatter): events = a
+    device int64 tensor [n, 20], the executor's records as ExecutedShard.events holds them. Returns {bin name: int64 tensor [count,
+    words]} for the 29 bins of RV64_BINS — the chips' record streams in execution order, ready for tracegen_riscv_alu / _mem / _divrem /
+    _alu_x0 / _syscall_instrs / _syscall_core / _state_bump / _memory_bump — all views of one arena sized exactly. Between the two
+    calls the 29 counts are read back (116 bytes): they decide the tables' heights."""
+    n = int(events.shape[0])
+    assert events.dtype == torch.int64 and (n == 0 or (events.is_cuda and events.shape[1] == RV64_EVENT_WORDS and events.is_contiguous()))
+    L, sp = _L(), _stream_ptr(stream)
+    device = events.device if n else torch.device("cuda", torch.cuda.current_device())
+    if n == 0:
+        return {name: torch.empty((0, w), dtype=torch.int64, device=device) for name, w in zip(RV64_BINS, RV64_BIN_WORDS)}
+    with torch.cuda.stream(stream or torch.cuda.current_stream()):
+        scratch = torch.empty(int(L.sp1hip_rv64_partition_scratch_bytes(n)) // 4, dtype=torch.int32, device=device)
+        d_counts = torch.empty(32, dtype=torch.int32, device=device)
+        check(L.sp1hip_rv64_partition_count(_dptr(events), n, _dptr(scratch), _dptr(d_counts), sp))
+        counts = [int(c) for c in d_counts[:len(RV64_BINS)].cpu()]          # synchronises the stream
+        total = sum(c * w for c, w in zip(counts, RV64_BIN_WORDS))
+        arena = torch.empty(total, dtype=torch.int64, device=device)
+        check(L.sp1hip_rv64_partition_scatter(_dptr(events), n, _dptr(scratch), _dptr(d_counts), _dptr(arena) if total else None, total, sp))
+    out, at = {}, 0
+    for name, c, w in zip(RV64_BINS, counts, RV64_BIN_WORDS):
+        out[name] = arena[at:at + c * w].view(c, w)
+        at += c * w
+    return out
+
+
+def tracegen_riscv_syscall_instrs(events, height, stream=None):
+    """`generate_trace_device` for the SyscallInstrs chip (sp1hip_tracegen_riscv_syscall_instrs): events = a device int64 tensor [n, 11]
+    of the ECALLs' sp1hip_rv64_alu_event_t records (bin "SyscallInstrs" of partition_rv64_events); returns the column-major
+    [65][height] table as a ColMajor, zero padding rows."""
+    return _tracegen_alu_records("sp1hip_tracegen_riscv_syscall_instrs", events, height, stream)
+
+
+def tracegen_riscv_syscall_core(events, height, global_events=None, stream=None):
+    """The same for the SyscallCore chip (bin "SyscallCore"): column-major [10][height]. `global_events`: an int32 device tensor
+    [n, 9] that receives the rows' Global events in the form tracegen_riscv_global reads — the tail tracegen_riscv_memory_local leaves
+    for them — or None."""
+    width = _L().sp1hip_tracegen_riscv_syscall_core_width()
+    n = int(events.shape[0])
+    assert events.dtype == torch.int64 and (n == 0 or (events.is_cuda and events.shape[1] == ALU_EVENT_WORDS and events.is_contiguous()))
+    if global_events is not None:
+        assert global_events.dtype == torch.int32 and tuple(global_events.shape) == (n, GLOBAL_EVENT_WORDS) and global_events.is_contiguous()
+    out = device_words(width * int(height))
+    check(_L().sp1hip_tracegen_riscv_syscall_core(_dptr(out), int(height), _dptr(events) if n else None, n,
+                                                  _dptr(global_events) if n and global_events is not None else None, _stream_ptr(stream)))
+    return ColMajor(out, int(height), width)
+
+
+def _tracegen_bump(fn, records, height, stream):
+    width = getattr(_L(), fn + "_width")()
+    n = int(records.shape[0])
+    assert records.dtype == torch.int64 and (n == 0 or (records.is_cuda and records.shape[1] == 4 and records.is_contiguous()))
+    out = device_words(width * int(height))
+    check(getattr(_L(), fn)(_dptr(out), int(height), _dptr(records) if n else None, n, _stream_ptr(stream)))
+    return ColMajor(out, int(height), width)
+
+
+def tracegen_riscv_state_bump(records, height, stream=None):
+    """`generate_trace_device` for the StateBump chip (sp1hip_tracegen_riscv_state_bump): records = a device int64 tensor [n, 4] (clk, pc,
+    next_pc, clock step | pc_carry << 32: bin "StateBump"); column-major [14][height], zero padding rows."""
+    return _tracegen_bump("sp1hip_tracegen_riscv_state_bump", records, height, stream)
+
+
+def tracegen_riscv_memory_bump(records, height, stream=None):
+    """The same for the MemoryBump chip (records: register, previous timestamp, value, window start — bin "MemoryBump"):
+    column-major [15][height]."""
+    return _tracegen_bump("sp1hip_tracegen_riscv_memory_bump", records, height, stream)
+
+
 KECCAK_EVENT_WORDS = 77                                                            # SP1HIP_RV64_KECCAK_WORDS
 
 

@@ -433,6 +433,17 @@ def global_events_9(events11):
     return torch.cat([ev[:, :8], (ev[:, 9] | (ev[:, 10] << 8))[:, None]], dim=1).to(torch.int32)
 
 
+def global_digest(table, count):
+    """The digest a device-made Global table (api.ColMajor) accumulates to: its row count - 1's accumulation.cumulative_sum_x / _y,
+    14 canonical words read back; the curve's start point when there is no event."""
+    if not count:
+        return [int(v) for xy in R.CURVE_CUMULATIVE_SUM_START for v in xy]
+    lay = R.chip("Global")[0].layout
+    cols = [lay["accumulation.cumulative_sum_" + axis] + j for axis in "xy" for j in range(7)]
+    words = table.words.view(table.width, table.height)[cols, count - 1].cpu().numpy().view(np.uint32).astype(np.uint64)
+    return [int(v) for v in words * np.uint64(pow(1 << 32, -1, P)) % np.uint64(P)]
+
+
 def core_device_tables_rest(shard, heights, syscall_global_events=None, stream=None):
     """The DivRem, AluX0, MemoryLocal and Global tables of a core shard, made on the device: ({name: api.ColMajor} for each of them
     with a non-zero entry in `heights` ({name: rows of its table, padding included}), (global_count, digest[14])). `shard`: an
@@ -464,7 +475,7 @@ def _core_device_tables_rest(shard, heights, syscall_global_events, stream):
     local = torch.as_tensor(shard.local).reshape(-1, 5)
     local = (local if local.is_cuda else local.cuda()).contiguous()
     count = 2 * int(local.shape[0]) + m
-    digest = [int(v) for xy in R.CURVE_CUMULATIVE_SUM_START for v in xy]
+    digest = global_digest(None, 0)
     if heights.get("MemoryLocal"):
         out["MemoryLocal"], gev = api.tracegen_riscv_memory_local(local, int(heights["MemoryLocal"]), extra_global_events=m, stream=stream)
     if heights.get("Global"):
@@ -473,12 +484,8 @@ def _core_device_tables_rest(shard, heights, syscall_global_events, stream):
             gev = torch.zeros((m, api.GLOBAL_EVENT_WORDS), dtype=torch.int32, device="cuda")
         if m:
             gev[count - m:] = global_events_9(torch.as_tensor(syscall_global_events)).to(gev.device)
-        table = out["Global"] = api.tracegen_riscv_global(gev, int(heights["Global"]), stream=stream)
-        if count:
-            lay = R.chip("Global")[0].layout
-            cols = [lay["accumulation.cumulative_sum_" + axis] + j for axis in "xy" for j in range(7)]
-            words = table.words.view(table.width, table.height)[cols, count - 1].cpu().numpy().view(np.uint32).astype(np.uint64)
-            digest = [int(v) for v in words * np.uint64(pow(1 << 32, -1, P)) % np.uint64(P)]
+        out["Global"] = api.tracegen_riscv_global(gev, int(heights["Global"]), stream=stream)
+        digest = global_digest(out["Global"], count)
     return out, (count, digest)
 
 
@@ -505,6 +512,78 @@ def device_lookup_tables(machine, tables, publics, shard_events, program, pc_bas
     if shard_events is not None and len(shard_events):
         counter.add_program_counters(shard_events, pc_base, n_instructions)
     return counter.finish()
+
+
+def global_events_11(events9):
+    """The inverse of global_events_9: [m, 9] int32 -> [m, 11] int64 (message[8], is_send, is_receive, kind), the form
+    global_events_balance and the host tracer speak."""
+    ev = events9.to(torch.int64)
+    recv = ev[:, 8] & 1
+    return torch.cat([ev[:, :8], (1 - recv)[:, None], recv[:, None], (ev[:, 8] >> 8)[:, None]], dim=1)
+
+
+def preprocessed_tables(executor, device="cuda"):
+    """{"Byte", "Program", "Range": int64 [rows, width]}: the preprocessed tables of every shard of the executor's program — what a
+    proving key is made of, once per run (Tracer.byte_range_tables and program_table make the same three per shard)."""
+    dev = torch.device(device)
+    pc_base, program = executor.program()
+    byte, rng = RT.byte_range_preprocessed(dev)
+    return {"Program": RT.program_table(program, pc_base, dev)[0].prep, "Byte": byte, "Range": rng}
+
+
+def device_core_shard(executor, shard, prep, prev=None, stream=None):
+    """A provable core shard from the executor's records alone, every table made ON THE DEVICE: (machine, chips, publics, global
+    events) with machine = [(AirProgram, InteractionProgram)] in chip-name order — the shard's whole shape cluster —, chips =
+    [(air, it, main ColMajor, prep ColMajor or None)] in the same order, ready for api.ProvingKey.prove_shard, publics = the
+    PROOF_MAX_NUM_PVS canonical words, global events = the int32 device tensor [count, 9] the Global table was made from (MemoryLocal's
+    two per record, then SyscallCore's). `shard`: an ExecutedShard; `prep`: {"Byte", "Program", "Range": ColMajor}, the program's
+    preprocessed tables (preprocessed_tables, made once per run); `prev`: the previous core shard's public values or None.
+
+    The events and `local` are uploaded as they are; api.partition_rv64_events routes and packs them (one 116-byte readback: the 29
+    counts are the tables' heights, pad32 of each); the instruction chips, DivRem, AluX0, SyscallInstrs, SyscallCore, StateBump and
+    MemoryBump are made from views of the record arena, MemoryLocal from `local`, Global from the events the MemoryLocal and
+    SyscallCore kernels write, Byte / Range / Program by device_lookup_tables; the chips of the shape cluster without rows stand at
+    height zero. No EventTracer, no host table. MemoryBump's rows stand in the partition's order — by event, then slot A, B, C —
+    where the host tracer's stand chip by chip."""
+    from .. import api
+    with torch.cuda.stream(stream or torch.cuda.current_stream()):
+        events = torch.as_tensor(shard.events).reshape(-1, EV_WORDS)
+        events = (events if events.is_cuda else events.cuda()).contiguous()
+        local = torch.as_tensor(shard.local).reshape(-1, 5)
+        local = (local if local.is_cuda else local.cuda()).contiguous()
+        parts = api.partition_rv64_events(events, stream=stream)
+        made = {}
+        for name, rec in parts.items():
+            n = int(rec.shape[0])
+            if n == 0 or name == "SyscallCore":
+                continue
+            height = RT.pad32(n)
+            if name in api.RISCV_ALU_CHIPS:
+                made[name] = api.tracegen_riscv_alu(name, rec, height, stream=stream)
+            elif name in api.RISCV_MEM_CHIPS:
+                made[name] = api.tracegen_riscv_mem(name, rec, height, stream=stream)
+            else:
+                gen = {"DivRem": api.tracegen_riscv_divrem, "AluX0": api.tracegen_riscv_alu_x0, "SyscallInstrs": api.tracegen_riscv_syscall_instrs,
+                       "StateBump": api.tracegen_riscv_state_bump, "MemoryBump": api.tracegen_riscv_memory_bump}[name]
+                made[name] = gen(rec, height, stream=stream)
+        n_local, m = int(local.shape[0]), int(parts["SyscallCore"].shape[0])
+        count = 2 * n_local + m
+        made["MemoryLocal"], gev = api.tracegen_riscv_memory_local(local, RT.pad32(n_local), extra_global_events=m, stream=stream)
+        if m:
+            made["SyscallCore"] = api.tracegen_riscv_syscall_core(parts["SyscallCore"], RT.pad32(m), global_events=gev[2 * n_local:], stream=stream)
+        made["Global"] = api.tracegen_riscv_global(gev, RT.pad32(count), stream=stream)
+        pv = execution_public_values(shard, prev)
+        PVM.set_global(pv, count, global_digest(made["Global"], count))
+        publics = PVM.to_tensor(pv)
+        names = sorted(RT.smallest_cluster(set(made) | set(prep)))
+        machine = [R.chip(n) for n in names]
+        for a, _ in machine:
+            if a.name not in made and a.name not in prep:
+                assert a.prep_width == 0, a.name
+                made[a.name] = api.ColMajor(api.device_words(0), 0, a.main_width)
+        pc_base, program = executor.program()
+        made.update(device_lookup_tables(machine, {n: (t, prep.get(n)) for n, t in made.items()}, publics, events, program, pc_base, stream=stream))
+        return machine, [(a, it, made[a.name], prep.get(a.name)) for a, it in machine], publics, gev
 
 
 def execution_public_values(sh, prev=None):
@@ -565,7 +644,7 @@ def split_thresholds(program_rows):
     return out
 
 
-def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_events=None, secp_events=None):
+def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_events=None, secp_events=None, untraced_core=False):
     """Every shard of a run, in the order the reference's controller emits them: the core shards as the program executes
     (`(kind, machine, tables, publics, global events, ExecutedShard)` with kind = "core"), then one precompile shard for the
     KECCAK_PERMUTE, POSEIDON2, SHA_EXTEND and SHA_COMPRESS calls each if there were any ("keccak", "poseidon2", "sha_extend",
@@ -574,7 +653,9 @@ def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_e
     shards' septic-curve digests add up to. `core_limit`: only the first so many core shards are traced and yielded (the rest of
     the program still runs, so every precompile and memory shard is there). `keccak_events` / `secp_events`: a list that takes,
     per Keccak / secp256k1 shard yielded, the shard's event records (for secp256k1 a pair (kind, events)) — what device trace
-    generation makes the chip's table from."""
+    generation makes the chip's table from. `untraced_core`: the core shards are yielded UNTRACED — `("core", None, None, prev, None,
+    ExecutedShard)` with prev = the previous core shard's public-value words (None for the first) — for device_core_shard, which
+    makes machine, tables, public values and global events on the device; no EventTracer is built for them."""
     from . import riscv_more_trace as MT
     keccak, poseidon2, sha_extend, sha_compress, uint256, secp_add, secp_double = [], [], [], [], [], [], []
     families = {}
@@ -587,7 +668,9 @@ def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_e
         if ctx is None:                                      # what the shards without instructions take from the run (RunContext)
             pc_base, program = executor.program()
             ctx = RT.RunContext(program, pc_base, pc_start=shard.pc_start)
-        if keep:
+        if keep and untraced_core:
+            prev_before, prev_pv = prev_pv, execution_public_values(shard, prev_pv)
+        elif keep:
             tr = EventTracer(executor, shard, device, prev=prev_pv)
             machine, tables, publics = tr.build()
             prev_pv = tr.pv
@@ -609,7 +692,9 @@ def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_e
             secp_double.append(shard.secp256k1_double)
         for kind, evs in shard.families.items():
             families.setdefault(kind, []).append(evs)
-        if keep:
+        if keep and untraced_core:
+            yield "core", None, None, prev_before, None, shard
+        elif keep:
             yield "core", machine, tables, publics, tr.global_events, shard
             del tr, machine, tables
     limit = split_thresholds(executor.program()[1].shape[0])

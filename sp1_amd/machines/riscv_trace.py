@@ -657,6 +657,17 @@ def smallest_cluster(names):
     return min(fits, key=len)
 
 
+def byte_range_preprocessed(dev):
+    """The preprocessed columns of the Byte table ([2^16, 7]: b, c, and, or, xor, ltu, msb — bytes/trace.rs) and of the Range table
+    ([2^17, 2]: value, bits — range/trace.rs), canonical int64."""
+    bc = torch.arange(1 << 16, device=dev)
+    bb, cc = bc >> 8, bc & 0xFF
+    byte = torch.stack([bb, cc, bb & cc, bb | cc, bb ^ cc, (bb < cc).to(I64), bb >> 7], dim=1)
+    ri = torch.arange(1 << 17, device=dev)
+    bits = torch.where(ri == 0, torch.zeros_like(ri), (torch.log2(ri.clamp(min=1).to(torch.float64)).floor()).to(I64))
+    return byte, torch.stack([torch.where(ri == 0, torch.zeros_like(ri), ri - (1 << bits)), bits], dim=1)
+
+
 def program_table(program, pc_base, dev, executed_pc=None):
     """Program: one row per instruction of the text — `program` [n, 6] = (opcode, op_a, op_b, op_c, imm_b, imm_c), the
     transpiled instruction list — (program/trusted.rs:L80-L131); multiplicity = how often each pc of `executed_pc` occurs (none:
@@ -1381,13 +1392,7 @@ class Tracer:
         byte_air, byte_it = R.chip("Byte")
         range_air, range_it = R.chip("Range")
         bt, rt = Table(byte_air, 1 << 16, dev), Table(range_air, 1 << 17, dev)
-        bc = torch.arange(1 << 16, device=dev)
-        bb, cc = bc >> 8, bc & 0xFF
-        bt.prep[:, 0], bt.prep[:, 1], bt.prep[:, 2], bt.prep[:, 3], bt.prep[:, 4] = bb, cc, bb & cc, bb | cc, bb ^ cc
-        bt.prep[:, 5], bt.prep[:, 6] = (bb < cc).to(I64), bb >> 7
-        ri = torch.arange(1 << 17, device=dev)
-        bits = torch.where(ri == 0, torch.zeros_like(ri), (torch.log2(ri.clamp(min=1).to(torch.float64)).floor()).to(I64))
-        rt.prep[:, 0], rt.prep[:, 1] = torch.where(ri == 0, torch.zeros_like(ri), ri - (1 << bits)), bits
+        bt.prep[:], rt.prep[:] = byte_range_preprocessed(dev)
         senders = [(name, machine[name][1], tbl.main[:tbl.n], tbl.prep[:tbl.n] if tbl.prep is not None else None) for name, tbl in self.tables.items()]
         senders.append(("PublicValues", PVM.program()[1], PVM.row(publics, dev), None))
         for name, it, main_rows, prep_rows in senders:

@@ -11,9 +11,10 @@
 // File map
 //   gkr_kernels.hpp   every kernel and the descriptors the host fills for them (IntDesc .. OpenDesc)
 //   gkr_host.cpp      the interaction-variable rounds in AVX-512 (tables as coefficient planes)
+//   gkr_rounds_host.hpp   the closed forms of the row rounds from a pass's sums (host only; tests/native/gkr_rounds.hip)
 //   ext_host.hpp      the host field helpers shared with jagged.hip (Ext operators, eq tables, DeviceBuf, upload)
 //   gkr.hip (here)    the cubic interpolation and the proof's byte writer; Levels (the fraction tree's storage); plan_passes (pure host:
-//                     every pass's shape and descriptors); the closed forms of the row rounds; the two forms of the host
+//                     every pass's shape and descriptors); the two forms of the host
 //                     interaction rounds; GkrProver: one proof, a phase per member function, run in order by GkrProver::prove
 //
 // MI355X shape
@@ -52,6 +53,7 @@ void gkr_host_round_fold(const uint32_t* tab, uint32_t* out, size_t stride, size
 #include "tensor_table.hpp"
 #include "ext_host.hpp"
 #include "gkr_kernels.hpp"
+#include "gkr_rounds_host.hpp"
 
 namespace sp1hip {
 
@@ -64,7 +66,7 @@ namespace gkr {
 // ================================================================ host side
 using namespace ext_host;   // DeviceBuf, the Ext operators, ext_c, log2_ceil, partial_lagrange_host, eval_mle_host, upload
 
-using Poly4 = std::array<Ext, 4>;
+using gkr_rounds::Poly4;
 Ext poly_eval(const Poly4& c, const Ext& x) { return ((c[3] * x + c[2]) * x + c[1]) * x + c[0]; }
 
 // the cubic through (0, y0), (1, y1), (1/2, yh), (b, 0): Lagrange interpolation as the reference's
@@ -122,14 +124,16 @@ struct ChipInfo {
 };
 
 constexpr uint32_t MAX_TILES = 512;
+constexpr uint64_t GKR_LOOKAHEAD_DEFAULT = 4;                // rounds per flat pass (SP1HIP_GKR_LOOKAHEAD; HISTORY: the A/B runs of 2, 3 and 4)
 uint32_t tiles_for(uint64_t threads) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((threads + 255) / 256, 1), MAX_TILES); }
 
 // per global interaction: is_send, kind (canonical), multiplicity and values as (constant flag, words) — words = the vcol in
 // device form [n_terms, constant (Montgomery), n_terms x (is_main, column, weight (Montgomery))]
 struct ParsedInt { uint32_t is_send, kind; std::vector<uint32_t> mult; std::vector<std::vector<uint32_t>> values; };
 struct RoundOut { Ext n0, n1, d0, d1; std::vector<Poly4> polys; Ext claimed_sum, eval; std::vector<Ext> point; };
-// The passes of a layer with v row variables (two rounds per pass, gkr_pass): (fold 0, sum s0 = min(2, v)), then
-// (fold what was just summed, sum min(2, what remains)) until nothing remains; the last pass only folds.
+// The passes of a layer with v row variables: (fold 0, sum s0), then (fold what was just summed, sum what the planner takes of
+// what remains) until nothing remains; the last pass only folds. A pass sums two rounds (gkr_pass) — or up to `depth` rounds
+// where that keeps it a FLAT launch (gkr_pass_deep; choose_pass).
 struct PassShape { int fv, sv; bool first; uint32_t tiles, tile_size, total_slots; size_t flat_off; bool flat; };
 
 // ---- SP1HIP_GKR_DEBUG=1: host-side phase times on stderr (where a stage's non-kernel time goes). Off: a branch per call.
@@ -197,12 +201,50 @@ struct PassPlan {
     std::vector<PassDesc> all_descs;                         // K per pass, in launch order
     std::vector<uint16_t> flat_index;                        // FLAT launches: slot -> descriptor, all launches back to back
 };
-// passes of layers 1 .. L - 1: (0, .), the folds in pairs, the last fold
-size_t count_passes(int L) { size_t n = 0; for (int v = 1; v <= L - 1; v++) n += (size_t)(v + 1) / 2 + 1; return n; }
+// What the next pass of a layer sums. rows_in: every interaction's rows before the pass folds fv variables; left: the variables
+// unbound after that fold. The look-ahead `depth` (SP1HIP_GKR_LOOKAHEAD: 2, 3 or 4) is taken where the pass is FLAT at that depth
+// — its slots, rows rounded up to whole cells of 2^sv per interaction, fit one flat launch —, otherwise the pass sums two rounds as
+// it always did: the large passes are bound by their products, a deeper grid costs them more than a launch, and only the flat
+// passes (latency, not work) gain from running fewer of them. depth = 2 is the two-round plan, launch for launch.
+struct PassChoice { int sv; bool flat; uint64_t total_slots; };
+PassChoice choose_pass(const std::vector<uint32_t>& rows_in, int fv, int left, int depth, uint32_t flat_max_slots) {
+    auto total_slots = [&](int sv) {
+        uint64_t n = 0;
+        for (uint32_t rin : rows_in) { const uint32_t ro = (rin + (1u << fv) - 1) >> fv; n += ((ro + (1u << sv) - 1) >> sv) << sv; }
+        return n;
+    };
+    const bool index_fits = rows_in.size() <= 65536;         // flat_index entries are 16-bit
+    if (depth > 2 && left > 2) {
+        const int sv = std::min(depth, left);
+        const uint64_t n = total_slots(sv);
+        if (n <= flat_max_slots && index_fits) return PassChoice{sv, true, n};
+    }
+    const int sv = std::min(2, left);
+    const uint64_t n = total_slots(sv);
+    return PassChoice{sv, n <= flat_max_slots && index_fits, n};
+}
+// passes of layers 1 .. L - 1 (depth 2: (0, .), the folds in pairs, the last fold = v + 1 / 2 + 1 per layer): the walk of plan_passes
+// over the shapes alone, for the buffers that are taken before the plan is made
+size_t count_passes(const Levels& lv, uint32_t flat_max_slots, int depth) {
+    size_t n = 0;
+    std::vector<uint32_t> rows_in(lv.K);
+    for (int v = 1; v <= lv.L - 1; v++) {
+        for (uint32_t i = 0; i < lv.K; i++) rows_in[i] = (lv.rows_at(i, v + 1) + 1) / 2;
+        for (int t = v, fv = 0;;) {
+            const int sv = choose_pass(rows_in, fv, t - fv, depth, flat_max_slots).sv;
+            for (uint32_t& r : rows_in) r = (r + (1u << fv) - 1) >> fv;
+            t -= fv;
+            n++;
+            if (sv == 0) break;
+            fv = sv;
+        }
+    }
+    return n;
+}
 
 // scratch[b]: the folded tables (4 vectors per interaction, ping-pong); host_rows: where a layer's last fold (one row per
 // interaction) goes when it is published straight to the host (null: it stays in scratch)
-void plan_passes(const Levels& lv, uint32_t flat_max_slots, Ext* const (&scratch)[2], Ext* host_rows, PassPlan& plan) {
+void plan_passes(const Levels& lv, uint32_t flat_max_slots, int depth, size_t n_passes, Ext* const (&scratch)[2], Ext* host_rows, PassPlan& plan) {
     const uint32_t K = lv.K;
     auto scratch_ptr = [&](int b, uint32_t i, int which, const std::vector<size_t>& so) -> Ext* { return scratch[b] + 4 * so[i] + (size_t)which * (so[i + 1] - so[i]); };
     // workgroups of a large pass. While every workgroup paid an L2 write-back and a serialised ticket in its tail
@@ -211,20 +253,20 @@ void plan_passes(const Levels& lv, uint32_t flat_max_slots, Ext* const (&scratch
     // the real-chip shard (alternating runs on three boxes): 1024-3072 tiles are within 0.3 ms of each other, 4096 is 0.7-1.0 ms
     // slower over the stage, 8192 / 16384 1.4 / 3.2 ms slower — a pass carries more state per workgroup than a round kernel did.
     constexpr uint32_t TARGET_TILES = 2048;
-    plan.all_descs.reserve(count_passes(lv.L) * K);          // ~10 MB at 730 interactions: no regrowth copies while planning
+    plan.all_descs.reserve(n_passes * K);                    // ~10 MB at 730 interactions: no regrowth copies while planning
     std::vector<uint32_t> rows_in(K);
     std::vector<size_t> so_prev, so_next;
     for (int v = 1; v <= lv.L - 1; v++) {
         for (uint32_t i = 0; i < K; i++) rows_in[i] = (lv.rows_at(i, v + 1) + 1) / 2;
         int cur = 0, t = v, fv = 0, pass = 0;
         for (;;) {
-            const int sv = std::min(2, t - fv);              // variables left after this pass's fold: t - fv
+            const PassChoice choice = choose_pass(rows_in, fv, t - fv, depth, flat_max_slots);   // variables left after this pass's fold: t - fv
+            const int sv = choice.sv;
             const bool first = pass <= 1;                    // pass 0 only sums, so pass 1 still reads the level
             if (fv > 0) { so_next.assign(K + 1, 0); for (uint32_t i = 0; i < K; i++) so_next[i + 1] = so_next[i] + ((rows_in[i] + (1u << fv) - 1) >> fv); }
-            uint64_t total_slots = 0;
             auto slots_of = [&](uint32_t rin) -> uint32_t { const uint32_t ro = (rin + (1u << fv) - 1) >> fv; return ((ro + (1u << sv) - 1) >> sv) << sv; };
-            for (uint32_t i = 0; i < K; i++) total_slots += slots_of(rows_in[i]);
-            const bool flat = total_slots <= flat_max_slots && K <= 65536;
+            const uint64_t total_slots = choice.total_slots;
+            const bool flat = choice.flat;
             const uint32_t tile_size = flat ? 1u : (uint32_t)std::max<uint64_t>(256, ((total_slots + TARGET_TILES - 1) / TARGET_TILES + 255) / 256 * 256);
             const size_t flat_off = plan.flat_index.size();
             plan.all_descs.resize(plan.all_descs.size() + K);
@@ -243,7 +285,9 @@ void plan_passes(const Levels& lv, uint32_t flat_max_slots, Ext* const (&scratch
                 if (flat) plan.flat_index.insert(plan.flat_index.end(), n_tiles, (uint16_t)i);
                 tile0 += n_tiles;
             }
-            if (flat) plan.shapes.push_back(PassShape{fv, sv, first, std::max<uint32_t>((tile0 + 255) / 256, 1), tile_size, tile0, flat_off, true});
+            // slots per workgroup of a flat launch: 256, one lane per output row; a deep fold (gkr_pass_deep_fold) 64, four lanes per row
+            const uint32_t wg_slots = fv > 2 ? 64 : 256;
+            if (flat) plan.shapes.push_back(PassShape{fv, sv, first, std::max<uint32_t>((tile0 + wg_slots - 1) / wg_slots, 1), tile_size, tile0, flat_off, true});
             else plan.shapes.push_back(PassShape{fv, sv, first, std::max<uint32_t>(tile0, 1), tile_size, tile0, 0, false});
             if (fv > 0) { for (uint32_t i = 0; i < K; i++) rows_in[i] = (rows_in[i] + (1u << fv) - 1) >> fv; so_prev = so_next; cur ^= 1; }
             t -= fv;
@@ -277,46 +321,6 @@ struct LayerRounds {
         return a;
     }
 };
-
-// the cubic  scale (1 - pt + (2 pt - 1) X) (q0 + q1 X + q2 X^2)
-Poly4 eq_times_quadratic(const Ext& scale, const Ext& pt, const Ext (&q)[3]) {
-    const Ext e0 = scale * (kb::ext_one() - pt), e1 = scale * (pt + pt - kb::ext_one());
-    return Poly4{e0 * q[0], e0 * q[1] + e1 * q[0], e0 * q[2] + e1 * q[1], e1 * q[2]};
-}
-// the quadratic with values g0, g1 at 0, 1 and leading coefficient gi
-void quadratic(const Ext& g0, const Ext& g1, const Ext& gi, Ext (&q)[3]) { q[0] = g0; q[1] = g1 - g0 - gi; q[2] = gi; }
-Ext eval_quadratic(const Ext (&q)[3], const Ext& x) { return (q[2] * x + q[1]) * x + q[0]; }
-
-// The sv rounds of one pass from its sums S, in closed form (gkr_kernels.hpp, above gkr_pass). t = row variables still unbound:
-// the pass summed over row_point[t - 1] (the last unbound variable) and, sv == 2, row_point[t - 2]. PA = eq factor of the
-// row variables bound so far. a0, a1 come back as the challenges the next pass folds with.
-void row_rounds_closed_form(int sv, const Ext (&S)[10], const std::vector<Ext>& row_point, int t, Ext& PA, LayerRounds& lr, Ext& a0, Ext& a1) {
-    const Ext one = kb::ext_one(), pt_a = row_point[t - 1];
-    if (sv == 2) {
-        // S: G00 G10 G01 G11 | Gi0 Gi1 | G0i G1i | Gii | Seq (first index: the last variable). The padding cells carry
-        // F = 1, i.e. their eq mass on the constant coefficient: on the four finite grid points
-        const Ext pt_b = row_point[t - 2];
-        const Ext corr = one - S[9];
-        Ext c0[3], c1[3], ci[3];
-        quadratic(S[0] + corr, S[1] + corr, S[4], c0);             // G(X, 0)
-        quadratic(S[2] + corr, S[3] + corr, S[5], c1);             // G(X, 1)
-        quadratic(S[6], S[7], S[8], ci);                           // leading coefficient in Y
-        Ext h[3];
-        for (int k = 0; k < 3; k++) h[k] = c0[k] + pt_b * (c1[k] - c0[k]);
-        a0 = lr.finish_round(eq_times_quadratic(PA, pt_a, h), pt_a, PA);
-        const Ext g0 = eval_quadratic(c0, a0), g1 = eval_quadratic(c1, a0), gi = eval_quadratic(ci, a0);
-        Ext gy[3];
-        quadratic(g0, g1, gi, gy);                                 // G(a0, Y)
-        a1 = lr.finish_round(eq_times_quadratic(PA, pt_b, gy), pt_b, PA);
-    } else {
-        // S: G0 G1 | Gi | Seq
-        const Ext corr = one - S[3];
-        Ext h[3];
-        quadratic(S[0] + corr, S[1] + corr, S[2], h);
-        a0 = lr.finish_round(eq_times_quadratic(PA, pt_a, h), pt_a, PA);
-        a1 = kb::ext_zero();
-    }
-}
 
 constexpr size_t plane_stride(size_t n) { return ((n + 15) / 16) * 16 + 16; }     // words of one coefficient plane of an n-entry table (gkr_host.cpp)
 
@@ -507,6 +511,7 @@ struct GkrProver {
     struct Cloned { sp1hip_challenger_t* c = nullptr; ~Cloned() { sp1hip_challenger_free(c); } } clone;   // freed on every path
     sp1hip_challenger_t* ch = nullptr;                       // = clone.c: the transcript of this call
     uint32_t witness = 0, flat_max_slots = 0;
+    int lookahead = 2;                                       // rounds a flat pass may sum (SP1HIP_GKR_LOOKAHEAD)
     Ext alpha;
     std::vector<Ext> betas;
     std::vector<uint32_t> int_chip;                          // global interaction -> chip
@@ -620,7 +625,9 @@ struct GkrProver {
         // Their buffer is taken from the arena HERE, before anything of this call is enqueued, and the side stream waits for
         // this point of `s` — a recycled block's previous user is then out of the way (the arena orders reuse by stream).
         flat_max_slots = (uint32_t)env_uint("SP1HIP_GKR_FLAT_SLOTS", 65536);   // read per call (tests)
-        n_passes_total = count_passes(L);
+        // rounds per flat pass: 2 = the two-round plan; 3 / 4 = fewer, deeper passes in the latency-bound tails (choose_pass)
+        lookahead = (int)std::min<uint64_t>(std::max<uint64_t>(env_uint("SP1HIP_GKR_LOOKAHEAD", GKR_LOOKAHEAD_DEFAULT), 2), 4);   // read per call (tests)
+        n_passes_total = count_passes(lv, flat_max_slots, lookahead);
         SP1HIP_TRY(aux_stream_for(s, 2, &side, &side_ev));
         // (their buffers come from the SIDE stream's share of the arena: a recycled block's previous user ran on that stream,
         // so the copies need not wait for anything on `s`; the blocks go back when this call has seen its last result)
@@ -748,13 +755,21 @@ struct GkrProver {
         // a layer's last fold (one row per interaction) goes straight to the mailbox slot, 16-byte aligned behind word 0
         direct_final = (size_t)K * 16 + 4 <= MAILBOX_WORDS;
         Ext* const scratch_ext[2] = {scratch[0].ext(), scratch[1].ext()};
-        plan_passes(lv, flat_max_slots, scratch_ext, direct_final ? reinterpret_cast<Ext*>(mb.h_slot + 4) : nullptr, plan);
-        {   // partial sums: one slot per workgroup of the largest launch, 10 sums each
-            uint32_t max_tiles = 1;
-            for (auto& sh : plan.shapes) max_tiles = std::max(max_tiles, sh.tiles);
-            SP1HIP_TRY(d_partials.alloc((size_t)max_tiles * 160, s));
+        plan_passes(lv, flat_max_slots, lookahead, n_passes_total, scratch_ext, direct_final ? reinterpret_cast<Ext*>(mb.h_slot + 4) : nullptr, plan);
+        {   // partial sums: one slot per workgroup of a launch, 16 bytes per sum it hands over
+            size_t bytes = 160;
+            for (auto& sh : plan.shapes) {
+                bytes = std::max(bytes, (size_t)sh.tiles * 16 * pass_sums(sh.sv));
+                SP1HIP_GKR_REQUIRE(sh.flat || (sh.fv <= 2 && sh.sv <= 2), "internal error: a deep pass that is not flat");
+            }
+            SP1HIP_TRY(d_partials.alloc(bytes, s));
         }
         timer.mark("pass descriptors planned");
+        if (timer.on) {
+            size_t deep = 0;
+            for (auto& sh : plan.shapes) deep += sh.fv > 2 || sh.sv > 2;
+            fprintf(stderr, "[sp1hip gkr] %zu passes at look-ahead %d, of which %zu deep\n", plan.shapes.size(), lookahead, deep);
+        }
         SP1HIP_GKR_REQUIRE(plan.all_descs.size() == n_passes_total * K, "internal error: pass count");
         SP1HIP_TRY(side_stage.upload(d_all.p, plan.all_descs.data(), plan.all_descs.size() * sizeof(PassDesc)));
         SP1HIP_GKR_REQUIRE(plan.flat_index.size() * sizeof(uint16_t) <= d_flat.n, "internal error: flat index size");
@@ -794,7 +809,16 @@ struct GkrProver {
 #define SP1HIP_GKR_PASS(FV, SV, F, NB, FL) hipLaunchKernelGGL((gkr_pass<FV, SV, F, NB, FL>), dim3(shape.tiles), dim3(256), 0, s, d_descs, (const Ext*)d_eq_int.p, Tp, TLp, c0, c1, d_partials.u32(), rs, publish_rows ? mb.seq + 1 : rsync.seq, K, shape.tile_size, fa)
 #define SP1HIP_GKR_PASS_FL(FV, SV, F, NB) do { if (shape.flat) SP1HIP_GKR_PASS(FV, SV, F, NB, true); else SP1HIP_GKR_PASS(FV, SV, F, NB, false); } while (0)
 #define SP1HIP_GKR_PASS_SRC(FV, SV) do { if (nbase) SP1HIP_GKR_PASS_FL(FV, SV, true, true); else if (shape.first) SP1HIP_GKR_PASS_FL(FV, SV, true, false); else SP1HIP_GKR_PASS_FL(FV, SV, false, false); } while (0)
-    int launch_pass(size_t idx, int v, int t_after, const Ext& c0, const Ext& c1) {
+#define SP1HIP_GKR_DEEP_K(FV, SV, F, NB) hipLaunchKernelGGL((SP1HIP_GKR_DEEP_NAME(FV)<FV, SV, F, NB>), dim3(shape.tiles), dim3(256), 0, s, d_descs, (const Ext*)d_eq_int.p, Tp, TLp, ch, d_partials.u32(), rs, seq, fa)
+#define SP1HIP_GKR_DEEP_NAME(FV) SP1HIP_GKR_DEEP_NAME_##FV
+#define SP1HIP_GKR_DEEP_NAME_0 gkr_pass_deep
+#define SP1HIP_GKR_DEEP_NAME_2 gkr_pass_deep
+#define SP1HIP_GKR_DEEP_NAME_3 gkr_pass_deep_fold
+#define SP1HIP_GKR_DEEP_NAME_4 gkr_pass_deep_fold
+#define SP1HIP_GKR_DEEP_FIRST(FV, SV) else if (fv == FV && sv == SV) { if (nbase) SP1HIP_GKR_DEEP_K(FV, SV, true, true); else SP1HIP_GKR_DEEP_K(FV, SV, true, false); }
+#define SP1HIP_GKR_DEEP(FV, SV) else if (fv == FV && sv == SV) { if (nbase) SP1HIP_GKR_DEEP_K(FV, SV, true, true); else if (shape.first) SP1HIP_GKR_DEEP_K(FV, SV, true, false); else SP1HIP_GKR_DEEP_K(FV, SV, false, false); }
+    int launch_pass(size_t idx, int v, int t_after, const Ext (&a)[4]) {
+        const Ext &c0 = a[0], &c1 = a[1];
         const PassShape shape = plan.shapes[idx];
         const PassDesc* d_descs = (const PassDesc*)d_all.p + idx * K;
         const int fv = shape.fv, sv = shape.sv;
@@ -807,6 +831,18 @@ struct GkrProver {
         const Ext* Tp = sv > 0 ? d_T.ext() + (((size_t)1 << (t_after - sv)) - 1) : (const Ext*)nullptr;
         const Ext* TLp = sv > 0 ? d_TL.ext() + (((size_t)1 << (t_after - sv)) - 1) : (const Ext*)nullptr;
         ScopedTimer tm(fv == 0 ? "gkr_pass_sum" : sv == 0 ? "gkr_pass_fold" : "gkr_pass_fold_sum", s);
+        if (fv > 2 || sv > 2) {                              // up to four rounds per pass: flat launches only (choose_pass)
+            const DeepChallenges ch{{a[0], a[1], a[2], a[3]}};
+            const uint32_t seq = publish_rows ? mb.seq + 1 : rsync.seq;
+            if (false) {}
+            SP1HIP_GKR_DEEP_FIRST(0, 3) SP1HIP_GKR_DEEP_FIRST(0, 4)
+            SP1HIP_GKR_DEEP(2, 3) SP1HIP_GKR_DEEP(2, 4)
+            SP1HIP_GKR_DEEP(3, 0) SP1HIP_GKR_DEEP(3, 1) SP1HIP_GKR_DEEP(3, 2) SP1HIP_GKR_DEEP(3, 3)
+            SP1HIP_GKR_DEEP(4, 0) SP1HIP_GKR_DEEP(4, 1) SP1HIP_GKR_DEEP(4, 2) SP1HIP_GKR_DEEP(4, 3) SP1HIP_GKR_DEEP(4, 4)
+            else { set_error("internal error: GKR pass shape (%d, %d)", fv, sv); return SP1HIP_ERROR_RUNTIME; }
+            SP1HIP_LAUNCH_CHECK();
+            return SP1HIP_SUCCESS;
+        }
         if (fv == 0 && sv == 2) { if (nbase) SP1HIP_GKR_PASS_FL(0, 2, true, true); else SP1HIP_GKR_PASS_FL(0, 2, true, false); }
         else if (fv == 0 && sv == 1) { if (nbase) SP1HIP_GKR_PASS_FL(0, 1, true, true); else SP1HIP_GKR_PASS_FL(0, 1, true, false); }
         else if (fv == 2 && sv == 2) SP1HIP_GKR_PASS_SRC(2, 2);
@@ -817,6 +853,14 @@ struct GkrProver {
         SP1HIP_LAUNCH_CHECK();
         return SP1HIP_SUCCESS;
     }
+#undef SP1HIP_GKR_DEEP
+#undef SP1HIP_GKR_DEEP_FIRST
+#undef SP1HIP_GKR_DEEP_K
+#undef SP1HIP_GKR_DEEP_NAME
+#undef SP1HIP_GKR_DEEP_NAME_0
+#undef SP1HIP_GKR_DEEP_NAME_2
+#undef SP1HIP_GKR_DEEP_NAME_3
+#undef SP1HIP_GKR_DEEP_NAME_4
 #undef SP1HIP_GKR_PASS_SRC
 #undef SP1HIP_GKR_PASS_FL
 #undef SP1HIP_GKR_PASS
@@ -841,32 +885,36 @@ struct GkrProver {
         }
         EqTabs eq_tabs;                                      // built lazily, after the first pass of the layer has been launched
         Ext PA = k.one;                                      // eq factor of the row variables bound so far
-        Ext a0 = k.zero, a1 = k.zero;                        // the challenges the next pass folds with
+        Ext a[4] = {k.zero, k.zero, k.zero, k.zero};         // the challenges the next pass folds with
+        int folds = 0;                                       // folding passes so far: they alternate scratch[0], [1], ...
+        auto finish = [&lr](const Poly4& poly, const Ext& pt, Ext& eq_factor) { return lr.finish_round(poly, pt, eq_factor); };
         int t = v;                                           // row variables not yet bound by a FOLD
-        for (bool first_pass = true;; first_pass = false) {  // the passes of the layer (two rounds each)
+        for (bool first_pass = true;; first_pass = false) {  // the passes of the layer (two rounds each; up to four where flat)
             const size_t idx = launch_idx++;
             const int fv = plan.shapes[idx].fv, sv = plan.shapes[idx].sv;
             t -= fv;                                         // variables left once this pass has folded
+            folds += fv > 0;
             if (!simd && t == sv) par->wake();               // the helpers' wake-up hides behind the layer's last two passes
             timer.lap(first_pass ? GkrTimer::SKIP : GkrTimer::HOST);   // closed forms + transcript since the last hand-over
-            SP1HIP_TRY(launch_pass(idx, v, t, a0, a1));
+            SP1HIP_TRY(launch_pass(idx, v, t, a));
             timer.lap(GkrTimer::LAUNCH);
             if (first_pass) eq_tabs.build(int_point, simd);  // host work behind a running kernel
             if (sv == 0) break;
-            const int ns = sv == 2 ? 10 : 4;
-            uint32_t h_sums[40];
+            const int ns = pass_sums(sv);
+            uint32_t h_sums[4 * pass_sums(gkr_rounds::GRID_MAX_K)];
             timer.lap(GkrTimer::SKIP);
             SP1HIP_TRY(rsync.wait(h_sums, 4 * ns));
             timer.lap(GkrTimer::WAIT);
-            Ext S[10];
+            Ext S[pass_sums(gkr_rounds::GRID_MAX_K)];
             memcpy(S, h_sums, 16 * (size_t)ns);
-            row_rounds_closed_form(sv, S, row_point, t, PA, lr, a0, a1);
+            if (fv <= 2 && sv <= 2) gkr_rounds::row_rounds_closed_form(sv, S, row_point.data(), t, PA, finish, a);
+            else gkr_rounds::row_rounds_from_grid(sv, S, row_point.data(), t, PA, finish, a);
         }
         // the layer's last fold left one row per interaction: dense over 2^niv on the host
         std::vector<size_t> so(K + 1, 0);
         for (uint32_t i = 0; i < K; i++) so[i + 1] = so[i] + (lv.rows_at(i, v + 1) ? 1 : 0);     // (a chip without rows stays (0, 1))
         const size_t final_rows_total = so[K];
-        const int cur = (int)((((v + 1) / 2)) & 1) ^ 1;      // folding passes of the layer: ceil(v / 2); they alternate scratch[0], [1], ...
+        const int cur = (folds - 1) & 1;                     // where the last fold wrote
         std::vector<Ext> host(std::max<size_t>(final_rows_total, 1) * 4);
         if (direct_final) { SP1HIP_TRY(mb.wait_next(host.data(), final_rows_total * 16, 4)); rsync.pending = false; }
         else SP1HIP_TRY(mb.fetch(scratch[cur].p, final_rows_total * 16, host.data()));

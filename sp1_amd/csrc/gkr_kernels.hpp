@@ -1,5 +1,6 @@
 // sp1_amd/csrc/gkr_kernels.hpp — the device side of LogUp-GKR: the first layer and the fraction tree, the per-layer eq tables,
-// the two-rounds-per-pass sumcheck kernel (gkr_pass) and the trace openings, with the descriptors the host fills for them.
+// the two-rounds-per-pass sumcheck kernel (gkr_pass), its up-to-four-rounds forms for the flat launches (gkr_pass_deep,
+// gkr_pass_deep_fold) and the trace openings, with the descriptors the host fills for them.
 // Included by gkr.hip only (the prover and its launches; the layout and the shape of the stage are described there).
 #pragma once
 #include "device_ctx.hpp"
@@ -359,6 +360,8 @@ __global__ __launch_bounds__(256) void eq_layer_tables_kernel(PointArg pi, int n
 // The next pass folds with BOTH challenges while it loads (rows 4r .. 4r+3 -> row r; the half-folded layer is never
 // written) and accumulates the grid of the following two rounds from the folded rows in registers. A layer of v row
 // variables is 1 + ceil(v / 2) launches and hand-overs instead of v + 1, and every table is read once per TWO rounds.
+// (The tail of a layer — FLAT launches, latency and not work — goes further: up to four rounds per pass, "deep passes" below.
+// What is said here holds for every tiled pass and for the flat passes that sum and fold at most two rounds.)
 //
 // Work split: one LANE per OUTPUT ROW — the fold is embarrassingly parallel, every load is a coalesced 16 B / lane run in
 // the existing lane-blocked layouts (a lane reads 4 input rows = what one lane of the one-round kernels read), and the
@@ -599,6 +602,249 @@ __global__ __launch_bounds__(256) void gkr_pass(const PassDesc* __restrict__ des
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (threadIdx.x == 0 && rs_ticket_is_last_acq_rel(rs.counter, blockIdx.x, gridDim.x)) rs_publish_seq(rs.host_slot, seq);
+    }
+}
+
+// ================================================================ deep passes: up to four rounds per pass in the FLAT launches
+// Most launches of a proof are FLAT passes of a few busy lanes, and such a pass costs one latency chain — descriptor, rows, eq,
+// products, reduction, ticket, publish, host wake-up, transcript, next launch — whatever it computes. The only way to shorten a
+// layer's tail is fewer passes: the same identity as above holds for the last k unbound variables, G(X_1 .. X_k) is
+// multi-quadratic and known from its values on {0, 1, inf}^k (3^k sums; gkr_rounds_host.hpp turns them into k round
+// polynomials), and the next pass folds 2^k rows per output row with the k challenges. gkr_pass_deep is that pass for FV or
+// SV in {3, 4}, FLAT only (plan_passes emits it where the slots, in whole cells of 2^SV rows, fit a flat launch); the tiled
+// passes and every two-round flat pass stay gkr_pass, instruction for instruction.
+//
+// Fold: 2^FV input rows per output row as a binary tree (bit j of the input row index is the variable bound by challenge j),
+// fully unrolled and without a branch per row, so the loads are issued as early as the registers allow. FV = 2: a lane per
+// output row as in gkr_pass; FV = 3, 4 (gkr_pass_deep_fold): a lane per output row AND table.
+// Grid, SV >= 3: with w the cell's eq weight, F w = B d0 + A d1 (A = wl n0 + w d0, B = wl n1, as in grid_accumulate) and all
+// four of A, B, d0, d1 are multilinear in the cell's variables, so F w at a grid point is B_g d0_g + A_g d1_g with X_g the signed
+// sum of table X over the rows the point selects: axis at 0 / 1 fixes the row bit, axis at inf takes (bit 1) - (bit 0). The
+// cell's rows go to LDS once (row-major over the cells, so that lanes which work on the same point of neighbouring cells read
+// consecutive 16 B), then one (point, cell) pair per lane and step: 2^(number of inf axes) rows per table, two products. The
+// sign common to the four sums cancels in the products. The 256 >> SV cells of a point sit in consecutive lanes and are summed
+// by shuffles; the workgroup's 3^SV + 1 sums (the last is the eq mass of its real cells) meet in LDS and leave through
+// rs_finish_block_sums. Dependent steps on the critical chain: one LDS round trip, <= 2^SV adds per table, two products, log2
+// (256 >> SV) shuffles — against 7 products and the DPP exchanges of a two-round pass.
+struct DeepChallenges { Ext a[4]; };
+
+// load_row without a branch: a row past the table's end reads the last real row (rows_in >= 1) and is replaced by the padding
+// fraction afterwards — the 2^FV rows of a deep fold are 4 .. 8 loads each, and behind a branch per row every one of them would
+// expose its own memory latency; like this all of them are in flight before the first use
+template <bool FIRST, bool NBASE>
+__device__ __forceinline__ Row load_row_select(const PassDesc& d, uint32_t r) {
+    const bool live = r < d.rows_in;
+    const uint32_t rc = live ? r : d.rows_in - 1;
+    const Ext zero = kb::ext_zero(), one = kb::ext_one();
+    Row q;
+    bool live1 = live;
+    if (FIRST) {
+        const bool has1 = 2 * rc + 1 < d.rows_x;
+        const uint32_t ea = level_pos(2 * rc, d.rows_x), eb = level_pos(has1 ? 2 * rc + 1 : 2 * rc, d.rows_x);
+        q.n0 = load_n<NBASE>(d.src[0], ea); q.d0 = ld_ext((const Ext*)d.src[1], ea);
+        q.n1 = load_n<NBASE>(d.src[0], eb); q.d1 = ld_ext((const Ext*)d.src[1], eb);
+        live1 = live && has1;
+    } else {
+        const uint32_t rp = folded_pos(rc, d.rows_in);
+        q.n0 = ld_ext((const Ext*)d.src[0], rp); q.d0 = ld_ext((const Ext*)d.src[1], rp);
+        q.n1 = ld_ext((const Ext*)d.src[2], rp); q.d1 = ld_ext((const Ext*)d.src[3], rp);
+    }
+    return Row{sel_ext(live, q.n0, zero), sel_ext(live, q.d0, one), sel_ext(live1, q.n1, zero), sel_ext(live1, q.d1, one)};
+}
+
+// the (point, cell) steps of a deep grid take the points in the order of their number of inf axes, so that the lanes of a wave
+// (64 / CELLS neighbouring points) add up the same number of rows: entry = point | rows fixed at one << 7 | inf axes << 11
+template <int SV> struct DeepPoints {
+    uint16_t e[81];
+    constexpr DeepPoints() : e{} {
+        int n = 0, np = 1;
+        for (int j = 0; j < SV; j++) np *= 3;
+        for (int m = 0; m <= SV; m++)
+            for (int p = 0; p < np; p++) {
+                int base = 0, inf = 0, cnt = 0;
+                for (int a = 0, x = p; a < SV; a++, x /= 3) { base |= (x % 3 == 1) << a; inf |= (x % 3 == 2) << a; cnt += x % 3 == 2; }
+                if (cnt == m) e[n++] = (uint16_t)(p | base << 7 | inf << 11);
+            }
+    }
+};
+template <int SV> __device__ const DeepPoints<SV> deep_points_table{};
+
+template <int LV, bool FIRST, bool NBASE>
+__device__ __forceinline__ Row fold_rows_deep(const PassDesc& d, uint32_t r0, const DeepChallenges& ch) {
+    if constexpr (LV == 0) return load_row_select<FIRST, NBASE>(d, r0);
+    else {
+        const Row lo = fold_rows_deep<LV - 1, FIRST, NBASE>(d, r0, ch), hi = fold_rows_deep<LV - 1, FIRST, NBASE>(d, r0 + (1u << (LV - 1)), ch);
+        if constexpr (LV == 1) return lerp_row_in<NBASE>(lo, hi, ch.a[0]);
+        else return lerp_row(lo, hi, ch.a[LV - 1]);
+    }
+}
+
+constexpr int deep_points(int sv) { int n = 1; for (int j = 0; j < sv; j++) n *= 3; return n; }
+// sums a pass hands over: the two-round forms' 4 / 10 (GridOut), a deep grid's 3^SV + 1 (the same counts at SV = 1, 2)
+constexpr int pass_sums(int sv) { return sv == 0 ? 0 : deep_points(sv) + 1; }
+
+// The grid of a deep pass from LDS. The workgroup holds 256 / LPR rows (LPR lanes per row), i.e. CELLS = 256 / LPR >> SV whole
+// cells. Every lane hands in the values it owns of row `row` (tables: [0] + [1] = A, [2] = B, [3] = d0, [4] = d1; bit t of
+// `owns`), the lane that owns a cell's first row its eq weight; then one (point, cell) pair per lane and step, the cells of a
+// point summed by shuffles, and the workgroup's 3^SV + 1 sums leave through rs_finish_block_sums.
+template <int SV, int LPR>
+__device__ __forceinline__ void deep_grid_finish(const Ext (&vals)[5], uint32_t owns, uint32_t row, bool owns_w, const Ext& w,
+                                                 uint32_t* __restrict__ partials, RoundSync rs, uint32_t seq) {
+    constexpr int CELLS = (256 / LPR) >> SV, ROWS = 1 << SV, NP = deep_points(SV), NS = NP + 1, STRIDE = CELLS + 1;
+    constexpr int STEPS = (NS * CELLS + 255) / 256;
+    static_assert(CELLS >= 1 && CELLS <= 32, "the cells of a point sit inside one wave");
+    __shared__ Ext sm_row[5][ROWS * STRIDE];                 // at [row of the cell][cell]
+    __shared__ Ext sm_w[CELLS];
+    __shared__ uint32_t sm_sums[4 * NS];
+    const uint32_t my = (row & (ROWS - 1u)) * STRIDE + (row >> SV);
+#pragma unroll
+    for (int t = LPR == 1 ? 1 : 0; t < 5; t++)
+        if ((owns >> t) & 1u) sm_row[t][my] = vals[t];
+    if (LPR == 1) sm_row[0][my] = vals[0];
+    if (owns_w) sm_w[row >> SV] = w;
+    __syncthreads();
+#pragma unroll
+    for (int step = 0; step < STEPS; step++) {
+        const uint32_t id = step * 256 + threadIdx.x, slot = id / CELLS, cell = id % CELLS;
+        uint32_t point = slot;                               // (slot NP: the eq mass)
+        Ext v = kb::ext_zero();
+        if (slot < (uint32_t)NP) {
+            const uint32_t entry = deep_points_table<SV>.e[slot];
+            point = entry & 127u;
+            const uint32_t base = (entry >> 7) & 15u, inf = entry >> 11;   // row bits the point fixes at one; axes it takes the difference over
+            Ext gA = kb::ext_zero(), gB = gA, g0 = gA, g1 = gA;
+            uint32_t s = 0;
+            do {                                             // the subsets s of inf: row base | s, sign (-1)^|s|
+                const uint32_t at = (base | s) * STRIDE + cell;
+                const Ext rA = LPR == 1 ? sm_row[0][at] : kb::ext_add(sm_row[0][at], sm_row[1][at]);
+                if (__popc(s) & 1) { gA = kb::ext_sub(gA, rA); gB = kb::ext_sub(gB, sm_row[2][at]); g0 = kb::ext_sub(g0, sm_row[3][at]); g1 = kb::ext_sub(g1, sm_row[4][at]); }
+                else { gA = kb::ext_add(gA, rA); gB = kb::ext_add(gB, sm_row[2][at]); g0 = kb::ext_add(g0, sm_row[3][at]); g1 = kb::ext_add(g1, sm_row[4][at]); }
+                s = (s - inf) & inf;
+            } while (s != 0);
+            v = kb::ext_add(kb::ext_mul(gB, g0), kb::ext_mul(gA, g1));
+        } else if (slot == (uint32_t)NP) v = sm_w[cell];
+        // every lane of the wave takes part: the CELLS lanes of a point are consecutive and aligned
+#pragma unroll
+        for (int off = CELLS / 2; off >= 1; off >>= 1)
+#pragma unroll
+            for (int k = 0; k < 4; k++) v.c[k] = kb::add(v.c[k], __shfl_xor(v.c[k], off, 64));
+        if (cell == 0 && slot < (uint32_t)NS)
+#pragma unroll
+            for (int k = 0; k < 4; k++) sm_sums[4 * point + k] = v.c[k];
+    }
+    __syncthreads();
+    rs_finish_block_sums<NS>(sm_sums, partials, blockIdx.x, gridDim.x, rs, seq);
+}
+
+// FV in {0, 2}, SV in {3, 4}: one lane per output row (256 slots per workgroup), the fold of gkr_pass
+template <int FV, int SV, bool FIRST, bool NBASE>
+__global__ __launch_bounds__(256) void gkr_pass_deep(const PassDesc* __restrict__ descs, const Ext* __restrict__ eq_int,
+                                                     const Ext* __restrict__ T, const Ext* __restrict__ TL, DeepChallenges ch,
+                                                     uint32_t* __restrict__ partials, RoundSync rs, uint32_t seq, FlatArgs fa) {
+    static_assert(FV <= 2 && SV > 2 && SV <= 4, "the two-round forms are gkr_pass, the deep folds gkr_pass_deep_fold");
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    const bool valid = p < fa.total_slots;                   // slots come in whole cells: a cell's lanes are valid together
+    const PassDesc d = descs[valid ? fa.index[p] : 0];
+    const uint32_t ro = p - d.tile0;
+    const uint32_t rows_out = (d.rows_in + (1u << FV) - 1u) >> FV;
+    Row row = padding_row();                                 // rows past rows_out inside a real cell are padding
+    if (valid && ro < rows_out) {
+        row = fold_rows_deep<FV, FIRST, NBASE>(d, ro << FV, ch);
+        if (FV > 0) {
+            const uint32_t rq = folded_pos(ro, rows_out);
+            st_ext(d.dst[0], rq, row.n0); st_ext(d.dst[1], rq, row.d0); st_ext(d.dst[2], rq, row.n1); st_ext(d.dst[3], rq, row.d1);
+        }
+    }
+    const uint32_t cells = (rows_out + (1u << SV) - 1u) >> SV, c = ro >> SV;
+    Ext w = kb::ext_zero(), wl = kb::ext_zero();             // zero for lanes past the last real cell
+    if (valid && c < cells) {
+        const Ext wi = ld_ext(eq_int, d.eq_int_index);
+        w = kb::ext_mul(ld_ext(T, c), wi); wl = kb::ext_mul(ld_ext(TL, c), wi);
+    }
+    constexpr bool NB = FIRST && NBASE && FV == 0;           // the numerators are base-field words
+    const Ext A = kb::ext_add(NB ? kb::ext_mul_base(wl, row.n0.c[0]) : kb::ext_mul(row.n0, wl), kb::ext_mul(row.d0, w));
+    const Ext B = NB ? kb::ext_mul_base(wl, row.n1.c[0]) : kb::ext_mul(row.n1, wl);
+    const Ext vals[5] = {A, kb::ext_zero(), B, row.d0, row.d1};
+    deep_grid_finish<SV, 1>(vals, 0x1du, threadIdx.x, (threadIdx.x & ((1u << SV) - 1u)) == 0, w, partials, rs, seq);
+}
+
+// FV in {3, 4}: FOUR lanes per output row, lane q of the quad folds table q (n0, d0, n1, d1) alone. A deep fold is 2^FV - 1
+// products per table, and with one lane per row the 60 products of FV = 4 were the pass (a wave per SIMD, most SIMDs of the
+// device idle: (4, 4) measured 59 us against 27 for the same sums behind a two-round fold, and 24 like this); a quarter of that
+// chain per lane, 64 slots per workgroup. The products that weigh the row go the same way — lane 0 wl n0, lane 1 w d0, lane 2 wl n1 — and A is summed
+// where the grid is read. The sums come in grid order at every SV (the host reads them with row_rounds_from_grid).
+template <int LV, bool FIRST, bool BASE>
+__device__ __forceinline__ Ext fold_table_deep(const void* src, uint32_t q, uint32_t rows_in, uint32_t rows_x, uint32_t r0,
+                                               const DeepChallenges& ch, const Ext& pad) {
+    if constexpr (LV == 0) {
+        bool live = r0 < rows_in;
+        const uint32_t rc = live ? r0 : rows_in - 1;         // (rows_in >= 1: see load_row_select)
+        uint32_t pos;
+        if (FIRST) {                                         // row r = entries 2r, 2r + 1 of the level: lanes 0, 1 read the even one
+            const uint32_t e = 2 * rc + (q >> 1);
+            const bool has = e < rows_x;
+            live = live && has;
+            pos = level_pos(has ? e : 2 * rc, rows_x);
+        } else pos = folded_pos(rc, rows_in);
+        const Ext v = BASE ? kb::ext_from_base(gptr((const uint32_t*)src)[pos]) : ld_ext((const Ext*)src, pos);
+        return sel_ext(live, v, pad);
+    } else {
+        const Ext lo = fold_table_deep<LV - 1, FIRST, BASE>(src, q, rows_in, rows_x, r0, ch, pad);
+        const Ext hi = fold_table_deep<LV - 1, FIRST, BASE>(src, q, rows_in, rows_x, r0 + (1u << (LV - 1)), ch, pad);
+        return lerp(lo, hi, ch.a[LV - 1]);
+    }
+}
+
+template <int FV, int SV, bool FIRST, bool NBASE>
+__global__ __launch_bounds__(256) void gkr_pass_deep_fold(const PassDesc* __restrict__ descs, const Ext* __restrict__ eq_int,
+                                                          const Ext* __restrict__ T, const Ext* __restrict__ TL, DeepChallenges ch,
+                                                          uint32_t* __restrict__ partials, RoundSync rs, uint32_t seq, FlatArgs fa) {
+    static_assert(FV > 2 && FV <= 4 && SV <= 4, "the shallower folds are gkr_pass and gkr_pass_deep");
+    const uint32_t q = threadIdx.x & 3u, row_wg = threadIdx.x >> 2, p = blockIdx.x * 64 + row_wg;
+    const bool valid = p < fa.total_slots;                   // slots come in whole cells: a cell's lanes are valid together
+    const PassDesc& d = descs[valid ? fa.index[p] : 0];
+    const uint32_t rows_in = d.rows_in, ro = p - d.tile0;
+    const uint32_t rows_out = (rows_in + (1u << FV) - 1u) >> FV;
+    const Ext pad = (q & 1u) ? kb::ext_one() : kb::ext_zero();      // the padding fraction (0, 1)
+    Ext val = pad;                                           // rows past rows_out inside a real cell are padding
+    if (valid && ro < rows_out) {
+        const void* src = FIRST ? d.src[q & 1u] : d.src[q];
+        const uint32_t rows_x = FIRST ? d.rows_x : 0u;
+        if (FIRST && NBASE && (q & 1u) == 0) val = fold_table_deep<FV, FIRST, true>(src, q, rows_in, rows_x, ro << FV, ch, pad);
+        else val = fold_table_deep<FV, FIRST, false>(src, q, rows_in, rows_x, ro << FV, ch, pad);
+        if (SV > 0 || rs.host_slot == nullptr) st_ext(d.dst[q], folded_pos(ro, rows_out), val);
+    }
+    if constexpr (SV == 0) {
+        if (rs.host_slot != nullptr) {
+            // The layer's last fold, published from this kernel (see gkr_pass). The quad's first lane stores the whole row, one
+            // dword per 64 B of the slot and instruction as gkr_pass does: with each lane storing its own table — four lanes of
+            // an instruction in one 64 B line of uncached host memory — this launch measured 620 - 690 us instead of 22.
+            Ext t[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+                for (int k = 0; k < 4; k++) t[u].c[k] = __shfl(val.c[k], (int)((threadIdx.x & 60u) + u), 64);
+            if (q == 0 && valid && ro < rows_out) {
+                const uint32_t rq = folded_pos(ro, rows_out);
+                st_ext_host(d.dst[0], rq, t[0]); st_ext_host(d.dst[1], rq, t[1]); st_ext_host(d.dst[2], rq, t[2]); st_ext_host(d.dst[3], rq, t[3]);
+            }
+            // same tail as gkr_pass
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (threadIdx.x == 0 && rs_ticket_is_last_acq_rel(rs.counter, blockIdx.x, gridDim.x)) rs_publish_seq(rs.host_slot, seq);
+        }
+    } else {
+        const uint32_t cells = (rows_out + (1u << SV) - 1u) >> SV, c = ro >> SV;
+        Ext w = kb::ext_zero(), wl = kb::ext_zero();         // zero for lanes past the last real cell
+        if (valid && c < cells) {
+            const Ext wi = ld_ext(eq_int, d.eq_int_index);
+            w = kb::ext_mul(ld_ext(T, c), wi); wl = kb::ext_mul(ld_ext(TL, c), wi);
+        }
+        // lane 0: wl n0 -> [0]; lane 1: w d0 -> [1], d0 -> [3]; lane 2: wl n1 -> [2]; lane 3: d1 -> [4]
+        const Ext prod = q == 3 ? val : kb::ext_mul(val, q == 1 ? w : wl);
+        const Ext vals[5] = {prod, prod, prod, val, val};
+        const uint32_t owns = q == 0 ? 0x01u : q == 1 ? 0x0au : q == 2 ? 0x04u : 0x10u;
+        deep_grid_finish<SV, 4>(vals, owns, row_wg, q == 0 && (row_wg & ((1u << SV) - 1u)) == 0, w, partials, rs, seq);
     }
 }
 

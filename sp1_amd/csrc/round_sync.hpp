@@ -42,7 +42,7 @@ struct RoundSync {                       // device-visible handles
 
 constexpr uint32_t RS_GROUPS = 32, RS_GROUP_STRIDE = 64;             // counter words: group g at g * STRIDE, level 2 at GROUPS * STRIDE
 constexpr size_t RS_COUNTER_BYTES = (size_t)(RS_GROUPS + 1) * RS_GROUP_STRIDE * 4;
-constexpr size_t RS_SLOT_WORDS = 64;                                 // host slot: sequence number + up to 63 words of sums
+constexpr size_t RS_SLOT_WORDS = 512;                                // host slot: sequence number + up to 511 words of sums (a four-round LogUp-GKR pass: 82 x 4)
 
 // one lane per workgroup: true for the workgroup that arrives last; leaves every counter zero for the next launch
 __device__ __forceinline__ bool rs_ticket_is_last(uint32_t* counter, uint32_t block_linear, uint32_t total_blocks) {
@@ -138,6 +138,54 @@ __device__ __forceinline__ void rs_finish(const kb::Ext (&acc)[NS], uint32_t* __
         for (int i = 0; i < 4; i++) a = kb::add(a, sm[i][threadIdx.x]);
         rs.host_slot[1 + threadIdx.x] = a;
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the slot is uncached host memory: acknowledged stores are ordered before seq
+    __syncthreads();
+    if (threadIdx.x == 0) rs.host_slot[0] = seq;
+}
+
+// The same hand-over for a workgroup that already holds its NS sums in LDS (`sums`: 4 NS words, complete and behind a
+// barrier) — the deep LogUp-GKR passes hand over 28 or 82 sums, and 82 accumulators per lane reduced wave by wave would be 328
+// wave reductions. The last workgroup adds the partials up with wave w taking the workgroups b = w mod 4 and a lane the words
+// lane, lane + 64, ...: a chain of total_blocks / 4 additions behind batched loads. Same ordering argument as rs_finish.
+template <int NS>
+__device__ __forceinline__ void rs_finish_block_sums(const uint32_t* sums, uint32_t* __restrict__ partials, uint32_t block_linear,
+                                                     uint32_t total_blocks, RoundSync rs, uint32_t seq) {
+    constexpr int NW = 4 * NS, PER = (NW + 63) / 64;
+    static_assert(1 + NW <= (int)RS_SLOT_WORDS, "the host slot holds the sequence number and every sum");
+    __shared__ uint32_t sm[4][PER * 64];
+    __shared__ uint32_t last_flag;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int w = threadIdx.x; w < NW; w += 256) rs_store_partial(&partials[(size_t)block_linear * NW + w], sums[w]);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) last_flag = rs_ticket_is_last(rs.counter, block_linear, total_blocks);
+    __syncthreads();
+    if (!last_flag) return;
+    uint32_t acc[PER];
+#pragma unroll
+    for (int q = 0; q < PER; q++) acc[q] = 0;
+    // (eight workgroups' words are loaded before the first is added: a coherent load is a trip to memory, and one trip per
+    // workgroup in turn was most of a 250-workgroup pass)
+    constexpr uint32_t BATCH = 8;
+    for (uint32_t b0 = wave; b0 < total_blocks; b0 += 4 * BATCH) {
+        uint32_t v[BATCH][PER];
+#pragma unroll
+        for (uint32_t u = 0; u < BATCH; u++)
+#pragma unroll
+            for (int q = 0; q < PER; q++) {
+                const uint32_t b = b0 + 4 * u;
+                v[u][q] = b < total_blocks && q * 64 + lane < NW
+                    ? __hip_atomic_load(partials + (size_t)b * NW + q * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+            }
+#pragma unroll
+        for (uint32_t u = 0; u < BATCH; u++)
+#pragma unroll
+            for (int q = 0; q < PER; q++) acc[q] = kb::add(acc[q], v[u][q]);
+    }
+#pragma unroll
+    for (int q = 0; q < PER; q++) sm[wave][q * 64 + lane] = acc[q];
+    __syncthreads();
+    for (int w = threadIdx.x; w < NW; w += 256) rs.host_slot[1 + w] = kb::add(kb::add(sm[0][w], sm[1][w]), kb::add(sm[2][w], sm[3][w]));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the slot is uncached host memory: acknowledged stores are ordered before seq
     __syncthreads();
     if (threadIdx.x == 0) rs.host_slot[0] = seq;

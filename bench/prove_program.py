@@ -122,11 +122,14 @@ def main():
     ap.add_argument("--device-counts", action="store_true", help="core shards: count the Byte, Range and Program multiplicities on the device from "
                     "the tables that are proved (riscv_exec.device_lookup_tables) instead of taking the tracer's three main tables; with or "
                     "without --device-core, and the proofs are the same bytes")
-    ap.add_argument("--device-shard", action="store_true", help="core shards: make the WHOLE shard on the device from the executor's records "
-                    "(riscv_exec.device_core_shard: the event partition kernel, every chip's table, the public values' Global fields, the "
-                    "lookup counts) — no EventTracer and no host table is built for them; the public values are chained by the previous "
-                    "shard's, the Global events still join the run's balance check. MemoryBump's rows stand in another order than the "
-                    "host tracer's, so a shard that crosses 2^24 cycles proves to other bytes (the same statement)")
+    ap.add_argument("--device-shard", action="store_true", help="core, memory, Keccak and secp256k1 shards: make the WHOLE shard on the device "
+                    "from the executor's records (riscv_exec.device_core_shard: the event partition kernel, every chip's table, the public "
+                    "values' Global fields, the lookup counts; device_memory_shard: MemoryGlobalInit / Finalize from the run's address lists; "
+                    "device_precompile_shard: the wide tables, SyscallPrecompile, MemoryLocal from the calls' event records) — no tracer and "
+                    "no host table is built for them; the public values are chained by the previous shard's, the Global events still join "
+                    "the run's balance check. The other precompile kinds (SHA-256, Poseidon2, UINT256, the fifteen families) keep the host "
+                    "path. MemoryBump's rows stand in another order than the host tracer's, so a core shard that crosses 2^24 cycles proves "
+                    "to other bytes (the same statement)")
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--out", default="")
@@ -156,7 +159,8 @@ def main():
     keccak_events = [] if args.device_keccak and not args.dry_run else None
     secp_events = [] if args.device_secp and not args.dry_run else None
     gen = X.program_shards(ex, shard_cycles, device=device, core_limit=args.core_shards or None, keccak_events=keccak_events,
-                           secp_events=secp_events, untraced_core=args.device_shard)
+                           secp_events=secp_events, untraced_core=args.device_shard, untraced_memory=args.device_shard,
+                           untraced_precompile=set(X.DEVICE_PRECOMPILE_KINDS) if args.device_shard else ())
     while True:
         try:
             kind, machine, tabs, publics, gev, sh = next(gen)
@@ -168,6 +172,12 @@ def main():
                 pk_prep = {n: to_col_major(t) for n, t in X.preprocessed_tables(ex, "cuda").items()}
             machine, device_chips, publics, gev9 = X.device_core_shard(ex, sh, pk_prep, prev=publics)
             gev = X.global_events_11(gev9)
+        elif args.device_shard and kind == "memory":                    # untraced: the run's context, then device_memory_shard's arguments
+            machine, device_chips, publics, gev9 = X.device_memory_shard(*sh[:4], pk_prep, publics, previous_init=sh[4], previous_fin=sh[5])
+            gev, sh = X.global_events_11(gev9), None
+        elif args.device_shard and kind in X.DEVICE_PRECOMPILE_KINDS:   # untraced: the run's context, then the event records
+            machine, device_chips, publics, gev9 = X.device_precompile_shard(kind, sh, pk_prep, publics)
+            gev, sh = X.global_events_11(gev9), None
         if device == "cuda":
             torch.cuda.synchronize()
         t_build = time.perf_counter() - t_prev                          # executor + tables of this shard (the generator ran both)
@@ -206,13 +216,13 @@ def main():
             else:
                 assert sorted(a.name for a, _ in machine if tabs[a.name][0] is not None) == sorted(pk_prep), "a shard without the program's preprocessed chips"
                 chips = [(a, i, to_col_major(tabs[a.name][1]), pk_prep.get(a.name)) for a, i in machine]
-            if keccak_events is not None and kind == "keccak":
+            if keccak_events is not None and kind == "keccak" and device_chips is None:
                 from sp1_amd.machines import riscv_more_trace as MT
                 names = ("KeccakPermute", "KeccakPermuteControl")
                 made = dict(zip(names, MT.keccak_device_tables(keccak_events.pop(), [int(tabs[n][1].shape[0]) for n in names])))
                 chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
                 row["device_keccak"] = True
-            if secp_events is not None and kind in ("secp256k1_add", "secp256k1_double"):
+            if secp_events is not None and kind in ("secp256k1_add", "secp256k1_double") and device_chips is None:
                 from sp1_amd.machines import riscv_more_trace as MT
                 name, events = secp_events.pop()
                 assert name == kind

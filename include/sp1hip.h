@@ -622,6 +622,46 @@ int sp1hip_tracegen_riscv_syscall_core(uint32_t* d_table, uint32_t height, const
 int sp1hip_tracegen_riscv_state_bump(uint32_t* d_table, uint32_t height, const uint64_t* d_records, uint32_t n_records, sp1hip_stream_t stream);
 int sp1hip_tracegen_riscv_memory_bump(uint32_t* d_table, uint32_t height, const uint64_t* d_records, uint32_t n_records, sp1hip_stream_t stream);
 
+/* Device trace generation for the chips that close the shards WITHOUT instructions — a memory shard's two chips, and the three
+ * chips every precompile shard has around its own — so that those shards are made on the device from the executor's records, as a
+ * core shard is. The reference fills all of them on the host.
+ *   sp1hip_tracegen_riscv_memory_global  MemoryGlobalInit (finalize = 0) / MemoryGlobalFinalize (finalize = 1), width 30, one layout
+ *       for both (`generate_trace_into` of crates/core/machine/src/memory/global.rs): one row per address, from n_records x 3 u64
+ *       { addr, value, timestamp } in strictly increasing address order. Row i holds clk_high, clk_low, index = i, prev_addr[3] (record
+ *       i - 1's address; previous_addr for row 0: the last address of the previous memory shard, 0 for the first), addr[3], value[4],
+ *       value_lower / value_upper (bytes 4 and 5), is_real, is_comp = prev != 0 or i != 0, prev_valid = 1 - (prev == 0 and i != 0), the
+ *       IsZero operations (inverse, result) of prev_addr's limb sum and of the index, and lt_cols of prev < addr over four 16-bit limbs
+ *       (bit, u16_flags[4]: the most significant limb that differs, not_eq_inv, comparison_limbs[2]), all times is_comp. The order of
+ *       the addresses is not checked: a list that does not increase makes a row whose constraints fail. When d_global_events is not
+ *       null it receives the rows' Global events in the form sp1hip_tracegen_riscv_global reads, [n_records][9] words: message = 0, 0
+ *       (Init: timestamp zero whatever the clk columns hold) or clk_high, clk_low (Finalize), addr[3], value[0] + lower * 2^16, value[1] +
+ *       upper * 2^16, value[3]; word 8 = kind Memory << 8 (Init: a send) or 1 | kind Memory << 8 (Finalize: a receive).
+ *   sp1hip_tracegen_riscv_syscall_precompile  SyscallPrecompile, width 10 (syscall/chip.rs): clk_high, clk_low, syscall_id, arg1[3],
+ *       arg2[3], is_real — one row per call, from a precompile's event records as the executor leaves them (n_events x words_per_event
+ *       u64: word 0 the clk, word 1 the first pointer, word arg2_word the second, arg2_word = -1 for none). When d_global_events is not
+ *       null it receives [n_events][9] words: message = clk_high, clk_low, syscall_id + arg1[0] * 2^8, arg1[1], arg1[2], arg2[3]; word 8 =
+ *       1 | kind Syscall << 8 — the RECEIVE of what sp1hip_tracegen_riscv_syscall_core sends. Point it behind MemoryLocal's events.
+ *   sp1hip_precompile_local_records      the MemoryLocal records { addr, initial clk, initial value, final clk, final value } of the
+ *       words the calls touched, one per word of each call (not merged across calls), ready for sp1hip_tracegen_riscv_memory_local.
+ *       `segments`: a HOST array of n_segments (1 to 4) x 5 u32 { ptr_word, count, pairs_word, final_word or 0xFFFFFFFF, final_clk_delta },
+ *       read before the call returns. Word i < count of event e in segment s becomes record base_s + e * count_s + i, base_s = the sum
+ *       of n_events * count over the earlier segments: addr = ev[ptr_word] + 8 i, initial clk = ev[pairs_word + 2 i], initial value =
+ *       ev[pairs_word + 2 i + 1], final clk = ev[0] + final_clk_delta, final value = ev[final_word + i], or the initial value for
+ *       0xFFFFFFFF (words only read). Keccak: 77 words, { 1, 25, 2, 52, 1 }; secp256k1 add: 43 words, { 1, 8, 3, 35, 1 } and
+ *       { 2, 8, 19, none, 0 }; secp256k1 double: 26 words, { 1, 8, 2, 18, 0 }. d_records holds records_capacity records; the sum of
+ *       n_events * count are written. Every segment must lie inside the event record.
+ * Tables: column-major [width][height] Montgomery words, zero padding rows. Needs n <= height. All argument checks come before any
+ * launch; a null pointer is accepted only with nothing to read or write (d_global_events: always); height == 0 (no records) succeeds
+ * without a launch. The calls enqueue and return: they do not synchronise. */
+int sp1hip_tracegen_riscv_memory_global_width(void);       /* 30 */
+int sp1hip_tracegen_riscv_syscall_precompile_width(void);  /* 10 */
+int sp1hip_tracegen_riscv_memory_global(int finalize, uint32_t* d_table, uint32_t height, const uint64_t* d_records, uint32_t n_records,
+                                        uint64_t previous_addr, int32_t* d_global_events, sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_syscall_precompile(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, uint32_t words_per_event,
+                                             uint32_t syscall_id, int32_t arg2_word, int32_t* d_global_events, sp1hip_stream_t stream);
+int sp1hip_precompile_local_records(uint64_t* d_records, uint64_t records_capacity, const uint64_t* d_events, uint32_t n_events, uint32_t words_per_event,
+                                    const uint32_t* segments, uint32_t n_segments, sp1hip_stream_t stream);
+
 /* Device trace generation for the two chips of a KECCAK_PERMUTE precompile shard, from the executor's event records as they are
  * (sp1hip_rv64_keccak_events below: n_events x 77 u64 on the device — [0] clk, [1] state pointer, [2 + 2i] / [3 + 2i] the previous
  * timestamp and the word read of state word i < 25, [52 + i] the word written). The reference fills both tables on the host

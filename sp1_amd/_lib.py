@@ -261,6 +261,11 @@ PROTOTYPES = [
     ("sp1hip_tracegen_riscv_syscall_core", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
     ("sp1hip_tracegen_riscv_state_bump", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_memory_bump", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_memory_global_width", None, []),
+    ("sp1hip_tracegen_riscv_syscall_precompile_width", None, []),
+    ("sp1hip_tracegen_riscv_memory_global", None, [C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint64, _vp, _vp]),
+    ("sp1hip_tracegen_riscv_syscall_precompile", None, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, _vp, _vp]),
+    ("sp1hip_precompile_local_records", None, [_vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_keccak_width", None, []),
     ("sp1hip_tracegen_riscv_keccak_control_width", None, []),
     ("sp1hip_tracegen_riscv_keccak", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),

@@ -633,6 +633,74 @@ def tracegen_riscv_memory_local(records, height, extra_global_events=0, stream=N
     return ColMajor(out, int(height), MEMORY_LOCAL_WIDTH), events
 
 
+MEMORY_GLOBAL_RECORD_WORDS, MEMORY_GLOBAL_WIDTH = 3, 30
+MEMORY_GLOBAL_KINDS = {"init": 0, "finalize": 1}
+
+
+def tracegen_riscv_memory_global(kind, records, height, previous_addr, extra_global_events=0, stream=None):
+    """`generate_trace_device` for the MemoryGlobalInit (kind "init") / MemoryGlobalFinalize ("finalize") chip
+    (sp1hip_tracegen_riscv_memory_global): records = a device int64 tensor [n, 3] { addr, value, timestamp } in strictly increasing
+    address order (not checked here: a list that does not increase makes a row whose constraints fail), previous_addr = the last
+    address of the previous memory shard's chip (0 for the first). Returns (the column-major [30][height] table as a ColMajor, the
+    rows' Global events: an int32 device tensor [n + extra_global_events, 9] in the form tracegen_riscv_global reads, record i at
+    row i — Init sends at timestamp zero, Finalize receives at the record's; the `extra_global_events` rows behind them are the
+    caller's to fill and are zero)."""
+    n, extra = int(records.shape[0]), int(extra_global_events)
+    assert records.dtype == torch.int64 and (n == 0 or (records.is_cuda and records.shape[1] == MEMORY_GLOBAL_RECORD_WORDS and records.is_contiguous()))
+    out = device_words(MEMORY_GLOBAL_WIDTH * int(height))
+    events = torch.empty((n + extra, GLOBAL_EVENT_WORDS), dtype=torch.int32, device=out.device)
+    if extra:                                                 # the kernel writes every word of the first n rows
+        with torch.cuda.stream(stream or torch.cuda.current_stream()):
+            events[n:].zero_()
+    check(_L().sp1hip_tracegen_riscv_memory_global(MEMORY_GLOBAL_KINDS[kind], _dptr(out), int(height), _dptr(records) if n else None, n,
+                                                   int(previous_addr) & ((1 << 64) - 1), _dptr(events) if n else None, _stream_ptr(stream)))
+    return ColMajor(out, int(height), MEMORY_GLOBAL_WIDTH), events
+
+
+SYSCALL_PRECOMPILE_WIDTH = 10
+# kind: (u64 words per event record, syscall id, the event word of the second pointer or -1, the segments of
+# sp1hip_precompile_local_records: (ptr_word, count, pairs_word, final_word or None, final_clk_delta)) — what the host builders
+# riscv_more_trace.precompile_shard_from / secp256k1_add_shard_from / secp256k1_double_shard_from hand _close_precompile_shard
+PRECOMPILE_DESCRIPTORS = {"keccak": (77, 0x09, -1, ((1, 25, 2, 52, 1),)),
+                          "secp256k1_add": (43, 0x0A, 2, ((1, 8, 3, 35, 1), (2, 8, 19, None, 0))),
+                          "secp256k1_double": (26, 0x0B, -1, ((1, 8, 2, 18, 0),))}
+
+
+def tracegen_riscv_syscall_precompile(events, height, syscall_id, arg2_word=-1, global_events=None, stream=None):
+    """`generate_trace_device` for the SyscallPrecompile chip (sp1hip_tracegen_riscv_syscall_precompile): events = a device int64 tensor
+    [n, words] of a precompile's event records as the executor leaves them (word 0 the clk, word 1 the first pointer, word
+    `arg2_word` the second or -1). Returns the column-major [10][height] table as a ColMajor, one row per call. `global_events`: an
+    int32 device tensor [n, 9] that receives the rows' Global events — receives of kind Syscall — in the form tracegen_riscv_global
+    reads: the tail tracegen_riscv_memory_local leaves for them; or None."""
+    n = int(events.shape[0])
+    assert events.dtype == torch.int64 and events.dim() == 2 and (n == 0 or (events.is_cuda and events.is_contiguous()))
+    if global_events is not None:
+        assert global_events.dtype == torch.int32 and tuple(global_events.shape) == (n, GLOBAL_EVENT_WORDS) and global_events.is_contiguous()
+    out = device_words(SYSCALL_PRECOMPILE_WIDTH * int(height))
+    check(_L().sp1hip_tracegen_riscv_syscall_precompile(_dptr(out), int(height), _dptr(events) if n else None, n, int(events.shape[1]), int(syscall_id),
+                                                        int(arg2_word), _dptr(global_events) if n and global_events is not None else None,
+                                                        _stream_ptr(stream)))
+    return ColMajor(out, int(height), SYSCALL_PRECOMPILE_WIDTH)
+
+
+def precompile_local_records(events, segments, stream=None):
+    """The MemoryLocal records of the words a precompile's calls touched (sp1hip_precompile_local_records): events = a device int64
+    tensor [n, words] of event records, segments = up to four (ptr_word, count, pairs_word, final_word or None, final_clk_delta) —
+    PRECOMPILE_DESCRIPTORS has those of Keccak and secp256k1. Returns a device int64 tensor [n * sum of counts, 5] { addr, initial
+    clk, initial value, final clk, final value }, segment after segment, event by event inside each: what tracegen_riscv_memory_local
+    reads."""
+    n = int(events.shape[0])
+    assert events.dtype == torch.int64 and events.dim() == 2 and (n == 0 or (events.is_cuda and events.is_contiguous()))
+    flat = np.array([[p, c, q, 0xFFFFFFFF if f is None else f, d] for p, c, q, f, d in segments], dtype=np.uint32).reshape(-1)
+    total = n * sum(int(s[1]) for s in segments)
+    device = events.device if events.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.stream(stream or torch.cuda.current_stream()):
+        out = torch.empty((total, MEMORY_LOCAL_RECORD_WORDS), dtype=torch.int64, device=device)
+    check(_L().sp1hip_precompile_local_records(_dptr(out) if total else None, total, _dptr(events) if n else None, n, int(events.shape[1]),
+                                               flat.ctypes.data_as(C.POINTER(C.c_uint32)), len(segments), _stream_ptr(stream)))
+    return out
+
+
 RV64_EVENT_WORDS = 20                                                              # the executor's record (ExecutedShard.events)
 RV64_BINS = tuple(RISCV_ALU_CHIPS) + tuple(RISCV_MEM_CHIPS) + ("DivRem", "AluX0", "SyscallInstrs", "SyscallCore", "StateBump", "MemoryBump")
 RV64_BIN_WORDS = (ALU_EVENT_WORDS,) * 14 + (MEM_EVENT_WORDS,) * 9 + (ALU_EVENT_WORDS,) * 4 + (4, 4)    # u64 words of a bin's record

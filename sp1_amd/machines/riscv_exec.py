@@ -17,6 +17,7 @@ import ctypes as C
 import gzip
 import os
 import types
+from collections.abc import Mapping
 
 import numpy as np
 import torch
@@ -586,6 +587,110 @@ def device_core_shard(executor, shard, prep, prev=None, stream=None):
         return machine, [(a, it, made[a.name], prep.get(a.name)) for a, it in machine], publics, gev
 
 
+def _close_device_shard(made, prep, cluster, publics, ctx, stream):
+    """What device_memory_shard and device_precompile_shard end with: the cluster's chips without rows at height zero, the Byte /
+    Range / Program counts (device_lookup_tables; the shard executes nothing), the chips in name order."""
+    from .. import api
+    names = sorted(cluster)
+    machine = [R.chip(n) for n in names]
+    for a, _ in machine:
+        if a.name not in made and a.name not in prep:
+            assert a.prep_width == 0, a.name
+            made[a.name] = api.ColMajor(api.device_words(0), 0, a.main_width)
+    made.update(device_lookup_tables(machine, {n: (t, prep.get(n)) for n, t in made.items()}, publics, None, ctx.program, ctx.pc_base, stream=stream))
+    return machine, [(a, it, made[a.name], prep.get(a.name)) for a, it in machine]
+
+
+def _memory_global_records(addrs, recs, previous, which):
+    """[n, 3] int64 { addr, value, timestamp } of a memory shard's address list and its (value, timestamp) records, with the host
+    filler's two assertions (riscv_more_trace.memory_shard_from): the addresses increase strictly wherever a row is compared, and
+    the chain does not end on the uncompared row of address 0."""
+    addr = np.asarray(addrs, dtype=np.uint64).reshape(-1)
+    n = int(addr.shape[0])
+    rec = recs.astype(np.uint64) if isinstance(recs, np.ndarray) else np.array([[int(x) & ((1 << 64) - 1) for x in r] for r in recs], dtype=np.uint64)
+    rec = rec.reshape(n, 2)
+    if n:
+        prev = np.concatenate([np.array([previous], dtype=np.uint64), addr[:-1]])
+        comp = (prev != 0) | (np.arange(n) != 0)
+        assert bool((addr[comp] > prev[comp]).all()), "addresses must increase strictly"
+        assert bool(comp[-1]), "a memory shard whose only %s event is address 0 does not close its chain" % which
+    return np.ascontiguousarray(np.concatenate([addr[:, None], rec], axis=1).view(np.int64))
+
+
+def device_memory_shard(init_addrs, init_recs, fin_addrs, fin_recs, prep, ctx, previous_init=0, previous_fin=0, stream=None):
+    """A provable memory shard from the run's address lists alone, every table made ON THE DEVICE: (machine, chips, publics, global
+    events) in the shape of device_core_shard — machine = RT.MEMORY_CLUSTER in chip-name order, chips = [(air, it, main ColMajor, prep
+    ColMajor or None)], publics = the PROOF_MAX_NUM_PVS canonical words, global events = the int32 device tensor [count, 9] the Global
+    table was made from: MemoryGlobalInit's sends, then MemoryGlobalFinalize's receives. The arguments are memory_shard_from's:
+    `init_addrs` / `fin_addrs` strictly increasing addresses, `init_recs` / `fin_recs` [n, 2] (value, timestamp) of each, `previous_init` /
+    `previous_fin` the previous memory shard's last addresses, `ctx` the run's RunContext (program, final state); `prep`: {"Byte",
+    "Program", "Range": ColMajor} (preprocessed_tables).
+
+    The two lists are uploaded as [n, 3] records; api.tracegen_riscv_memory_global makes each chip's table and its Global events (a
+    kind without events stands at height zero and its chain stands still), api.tracegen_riscv_global the Global table and — read back,
+    14 words — the digest, device_lookup_tables the Byte / Range / Program counts. No Tracer, no host table."""
+    from .. import api
+    lists = (("MemoryGlobalInit", "init", init_addrs, init_recs, previous_init), ("MemoryGlobalFinalize", "finalize", fin_addrs, fin_recs, previous_fin))
+    host = [_memory_global_records(a, r, int(p), which) for _, which, a, r, p in lists]
+    pv = PVM.finalized_state(*ctx.final)
+    with torch.cuda.stream(stream or torch.cuda.current_stream()):
+        count = sum(int(h.shape[0]) for h in host)
+        gev = torch.empty((count, api.GLOBAL_EVENT_WORDS), dtype=torch.int32, device="cuda")
+        made, at = {}, 0
+        for (name, which, a_list, _, previous), rec in zip(lists, host):
+            n = int(rec.shape[0])
+            PVM.put(pv, "previous_%s_addr" % which, PVM.addr_limbs(previous))
+            PVM.put(pv, "last_%s_addr" % which, PVM.addr_limbs(int(rec[-1, 0]) if n else previous))
+            PVM.put(pv, "global_%s_count" % which, n)
+            if n == 0:
+                continue
+            made[name], ev = api.tracegen_riscv_memory_global(which, torch.from_numpy(rec).cuda(), RT.pad32(n), int(previous), stream=stream)
+            gev[at:at + n] = ev
+            at += n
+        made["Global"] = api.tracegen_riscv_global(gev, RT.pad32(count), stream=stream)
+        PVM.set_global(pv, count, global_digest(made["Global"], count))
+        publics = PVM.to_tensor(pv)
+        machine, chips = _close_device_shard(made, prep, RT.MEMORY_CLUSTER, publics, ctx, stream)
+        return machine, chips, publics, gev
+
+
+DEVICE_PRECOMPILE_KINDS = ("keccak", "secp256k1_add", "secp256k1_double")
+
+
+def device_precompile_shard(kind, events, prep, ctx, stream=None):
+    """A provable precompile shard of `kind` (DEVICE_PRECOMPILE_KINDS) from the executor's event records alone ([n, 77 / 43 / 26] int64,
+    numpy or torch), every table made ON THE DEVICE: (machine, chips, publics, global events) in the shape of device_core_shard. The
+    wide tables come from api.tracegen_riscv_keccak / _keccak_control / _secp256k1_add / _double; SyscallPrecompile
+    (api.tracegen_riscv_syscall_precompile) and the MemoryLocal records of the touched words (api.precompile_local_records, one
+    record per word of each call) from the same records by api.PRECOMPILE_DESCRIPTORS[kind]; MemoryLocal and Global as in a core
+    shard — MemoryLocal's two events per record first, then SyscallPrecompile's receives —; the public values are the program's
+    initial state with the Global fields set. No Tracer, no host table."""
+    from .. import api
+    words, syscall_id, arg2_word, segments = api.PRECOMPILE_DESCRIPTORS[kind]
+    with torch.cuda.stream(stream or torch.cuda.current_stream()):
+        ev = torch.as_tensor(np.ascontiguousarray(events) if isinstance(events, np.ndarray) else events).reshape(-1, words)
+        ev = (ev if ev.is_cuda else ev.cuda()).contiguous()
+        n = int(ev.shape[0])
+        assert n, "a precompile shard has at least one call"
+        if kind == "keccak":
+            made = {"KeccakPermute": api.tracegen_riscv_keccak(ev, RT.pad32(24 * n), stream=stream), "KeccakPermuteControl": api.tracegen_riscv_keccak_control(ev, RT.pad32(n), stream=stream)}
+        elif kind == "secp256k1_add":
+            made = {"Secp256k1AddAssign": api.tracegen_riscv_secp256k1_add(ev, RT.pad32(n), stream=stream)}
+        else:
+            made = {"Secp256k1DoubleAssign": api.tracegen_riscv_secp256k1_double(ev, RT.pad32(n), stream=stream)}
+        local = api.precompile_local_records(ev, segments, stream=stream)
+        n_local = int(local.shape[0])
+        count = 2 * n_local + n
+        made["MemoryLocal"], gev = api.tracegen_riscv_memory_local(local, RT.pad32(n_local), extra_global_events=n, stream=stream)
+        made["SyscallPrecompile"] = api.tracegen_riscv_syscall_precompile(ev, RT.pad32(n), syscall_id, arg2_word, global_events=gev[2 * n_local:], stream=stream)
+        made["Global"] = api.tracegen_riscv_global(gev, RT.pad32(count), stream=stream)
+        pv = PVM.no_memory_events(PVM.initialized_state(ctx.pc_start))
+        PVM.set_global(pv, count, global_digest(made["Global"], count))
+        publics = PVM.to_tensor(pv)
+        machine, chips = _close_device_shard(made, prep, RT.smallest_cluster(set(made) | set(prep)), publics, ctx, stream)
+        return machine, chips, publics, gev
+
+
 def execution_public_values(sh, prev=None):
     """An execution shard's `PublicValues` as the tracing executor leaves them (tracing.rs postprocess L548-L562, executor.rs:L60
     finalize_public_values(true)) with the previous shard's state threaded in (`prev`: its words, None for the first shard); the
@@ -627,24 +732,47 @@ PRECOMPILES = {"keccak": ("KeccakPermute", "KeccakPermuteControl", 24, 25), "pos
                    ("bn254_fp2_mul", 16), ("bls12381_fp2_mul", 24), ("ed_add", 16), ("ed_decompress", 8), ("uint256_ops", 20))}}
 
 
+class SplitThresholds(Mapping):
+    """split_thresholds' result: kind -> events per shard, each entry worked out when it is first asked for. A chip's cost is its
+    width, and transcribing every precompile chip to learn it takes seconds, which a run without such calls need not spend; iterating
+    (dict(thresholds), ==) works all of them out."""
+
+    def __init__(self, program_rows):
+        self.program_rows, self._known = program_rows, {}
+
+    def __getitem__(self, kind):
+        if kind not in self._known:
+            if kind != "memory" and kind not in PRECOMPILES:
+                raise KeyError(kind)
+            cost = lambda name: (lambda a: a.main_width + a.prep_width)(R.chip(name)[0])
+            trunc = lambda v: v // 32 * 32
+            area = ELEMENT_THRESHOLD - (-(-self.program_rows // 32) * 32 * cost("Program") + (1 << 16) * cost("Byte") + (1 << 17) * cost("Range"))
+            if kind == "memory":
+                self._known[kind] = trunc(min(area // (cost("MemoryGlobalInit") + cost("Global")), HEIGHT_THRESHOLD) // 2)
+            else:
+                chip_name, control, rows, touched = PRECOMPILES[kind]
+                per = rows * cost(chip_name) + (cost(control) if control else 0) + touched * cost("MemoryLocal") + 2 * touched * cost("Global")
+                per += cost("SyscallPrecompile") + cost("Global")
+                self._known[kind] = min(trunc(area // per), trunc(HEIGHT_THRESHOLD // max(rows, 2 * touched + 1)))
+        return self._known[kind]
+
+    def __iter__(self):
+        return iter(list(PRECOMPILES) + ["memory"])
+
+    def __len__(self):
+        return len(PRECOMPILES) + 1
+
+
 def split_thresholds(program_rows):
     """`SplitOpts::new` (core/executor/src/opts.rs:L186-L240): how many events of one system call, and how many memory
     initialise / finalise events, go into one shard — the trace area left beside the fixed tables divided by the cost of one event
     (its chip rows, control row, MemoryLocal / Global rows per touched address, SyscallPrecompile row: utils.rs:L117-L154),
-    bounded by the height limit, rounded down to 32."""
-    cost = lambda name: (lambda a: a.main_width + a.prep_width)(R.chip(name)[0])
-    trunc = lambda v: v // 32 * 32
-    area = ELEMENT_THRESHOLD - (-(-program_rows // 32) * 32 * cost("Program") + (1 << 16) * cost("Byte") + (1 << 17) * cost("Range"))
-    out = {}
-    for kind, (chip_name, control, rows, touched) in PRECOMPILES.items():
-        per = rows * cost(chip_name) + (cost(control) if control else 0) + touched * cost("MemoryLocal") + 2 * touched * cost("Global")
-        per += cost("SyscallPrecompile") + cost("Global")
-        out[kind] = min(trunc(area // per), trunc(HEIGHT_THRESHOLD // max(rows, 2 * touched + 1)))
-    out["memory"] = trunc(min(area // (cost("MemoryGlobalInit") + cost("Global")), HEIGHT_THRESHOLD) // 2)
-    return out
+    bounded by the height limit, rounded down to 32. A mapping over every kind of PRECOMPILES and "memory" (SplitThresholds)."""
+    return SplitThresholds(program_rows)
 
 
-def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_events=None, secp_events=None, untraced_core=False):
+def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_events=None, secp_events=None, untraced_core=False,
+                   untraced_memory=False, untraced_precompile=()):
     """Every shard of a run, in the order the reference's controller emits them: the core shards as the program executes
     (`(kind, machine, tables, publics, global events, ExecutedShard)` with kind = "core"), then one precompile shard for the
     KECCAK_PERMUTE, POSEIDON2, SHA_EXTEND and SHA_COMPRESS calls each if there were any ("keccak", "poseidon2", "sha_extend",
@@ -655,7 +783,12 @@ def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_e
     per Keccak / secp256k1 shard yielded, the shard's event records (for secp256k1 a pair (kind, events)) — what device trace
     generation makes the chip's table from. `untraced_core`: the core shards are yielded UNTRACED — `("core", None, None, prev, None,
     ExecutedShard)` with prev = the previous core shard's public-value words (None for the first) — for device_core_shard, which
-    makes machine, tables, public values and global events on the device; no EventTracer is built for them."""
+    makes machine, tables, public values and global events on the device; no EventTracer is built for them. `untraced_precompile`: a
+    set of kinds of DEVICE_PRECOMPILE_KINDS whose shards are yielded UNTRACED — `(kind, None, None, RunContext, None, events)` with
+    events = the shard's event records, an int64 array [n, 77 / 43 / 26] — for device_precompile_shard(kind, events, prep, ctx).
+    `untraced_memory`: the memory shards are yielded UNTRACED — `("memory", None, None, RunContext, None, (init_addrs, init_recs,
+    fin_addrs, fin_recs, previous_init, previous_fin))`, the arguments of device_memory_shard in its order (the RunContext holds the
+    run's final state); the two address chains are still threaded here. No Tracer is built for either."""
     from . import riscv_more_trace as MT
     keccak, poseidon2, sha_extend, sha_compress, uint256, secp_add, secp_double = [], [], [], [], [], [], []
     families = {}
@@ -697,9 +830,12 @@ def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_e
         elif keep:
             yield "core", machine, tables, publics, tr.global_events, shard
             del tr, machine, tables
-    limit = split_thresholds(executor.program()[1].shape[0])
+    limit = split_thresholds(executor.program()[1].shape[0])    # (a kind's threshold is worked out when a call of that kind asks for it)
     chunks = lambda kind, evs: (lambda a: [a[i:i + limit[kind]] for i in range(0, a.shape[0], limit[kind])])(np.concatenate(evs)) if evs else []
     for kk in chunks("keccak", keccak):
+        if "keccak" in untraced_precompile:
+            yield "keccak", None, None, ctx, None, kk
+            continue
         kk = torch.as_tensor(kk, device=device)
         rd = kk[:, 2:52].reshape(-1, 25, 2)
         machine, tables, publics, gev = MT.precompile_shard_from(kk[:, 0], kk[:, 1], rd[:, :, 1].contiguous(), rd[:, :, 0].contiguous(), device, ctx=ctx)
@@ -716,6 +852,10 @@ def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_e
                              ("uint256", uint256, MT.uint256_shard_from), ("secp256k1_add", secp_add, MT.secp256k1_add_shard_from),
                              ("secp256k1_double", secp_double, MT.secp256k1_double_shard_from)):
         for part in chunks(name, evs):
+            if name in untraced_precompile:
+                assert name in DEVICE_PRECOMPILE_KINDS, name
+                yield name, None, None, ctx, None, part
+                continue
             machine, tables, publics, gev = build(part, device, ctx=ctx)
             if secp_events is not None and name.startswith("secp256k1_"):
                 secp_events.append((name, part))
@@ -749,6 +889,11 @@ def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_e
     for at in range(0, fin_addr.shape[0], limit["memory"]):
         fa, fr = fin_addr[at:at + limit["memory"]], fin_rec[at:at + limit["memory"]]
         lo, hi = np.searchsorted(init_addr, fa[0], side="left"), np.searchsorted(init_addr, fa[-1], side="right")
+        if untraced_memory:
+            yield "memory", None, None, ctx, None, (init_addr[lo:hi], init_rec[lo:hi], fa, fr, previous_init, previous_fin)
+            previous_init = int(init_addr[hi - 1]) if hi > lo else previous_init
+            previous_fin = int(fa[-1])
+            continue
         machine, tables, publics, gev = MT.memory_shard_from(init_addr[lo:hi], init_rec[lo:hi], fr, device, previous_addr=previous_init, ctx=ctx,
                                                              fin_addrs=fa, previous_fin_addr=previous_fin)
         previous_init = int(init_addr[hi - 1]) if hi > lo else previous_init

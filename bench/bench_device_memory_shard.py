@@ -185,9 +185,10 @@ def main():
     ex = X.Executor(X.guest_file(args.program + ".elf"), stdin=stdin_of(args.program, args.cycles))
     ex.cut_by_area()
     t0 = time.perf_counter()
-    shards = [s for s in X.program_shards(ex, 1 << 40, core_limit=0, untraced_memory=True) if s[0] == "memory"]     # executed, nothing traced
+    shards = [r for r in X.run_records(ex, 1 << 40, core_limit=0) if r.kind == "memory"]     # executed, nothing traced
     log("%s executed in %.1f s: %d memory shard(s)" % (args.program, time.perf_counter() - t0, len(shards)))
-    ctx, lists = shards[0][3], shards[0][5]
+    r = shards[0]
+    ctx, lists = r.ctx, (r.init_addrs, r.init_recs, r.fin_addrs, r.fin_recs, r.previous_init, r.previous_fin)
     prep = {k: to_col_major(t) for k, t in X.preprocessed_tables(ex, "cuda").items()}
     out.update({"measured": True, "device_name": torch.cuda.get_device_name(0), "rounds": args.rounds, "program": args.program, "cycles_asked": args.cycles,
                 "memory_shards_of_the_run": len(shards)})

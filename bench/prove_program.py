@@ -106,24 +106,8 @@ def main():
     ap.add_argument("--in-flight", type=int, default=0, help="after the shard-by-shard pass, prove ALL shards again through the library's "
                     "prover pool with this many proofs in flight (tables resident in HBM; proofs must equal the first pass's)")
     ap.add_argument("--only-kinds", default="", help="comma-separated shard kinds: build every shard, prove only these (a profile of one kind)")
-    ap.add_argument("--device-keccak", action="store_true", help="Keccak shards: make the KeccakPermute / KeccakPermuteControl tables on the "
-                    "device from the executor's event records (api.tracegen_riscv_keccak) instead of taking the tracer's; the shard's "
-                    "other chips stay as they are, and the proofs are the same bytes")
-    ap.add_argument("--device-secp", action="store_true", help="secp256k1 shards: make the Secp256k1AddAssign / Secp256k1DoubleAssign table on "
-                    "the device from the executor's event records (api.tracegen_riscv_secp256k1_add / _double) instead of taking the "
-                    "tracer's; the shard's other chips stay as they are, and the proofs are the same bytes")
-    ap.add_argument("--device-core", action="store_true", help="core shards: make the tables of the fourteen ALU / branch / jump chips and the "
-                    "nine load and store chips on the device from the shard's event records (riscv_exec.core_device_tables) instead of "
-                    "taking the tracer's; the shard's other chips stay as they are, and the proofs are the same bytes")
-    ap.add_argument("--device-rest", action="store_true", help="core shards: make the DivRem, AluX0, MemoryLocal and Global tables on the device "
-                    "from the shard's event records and local-memory records (riscv_exec.core_device_tables_rest; the Global table from the "
-                    "events the MemoryLocal kernel writes, SyscallCore's appended) instead of taking the tracer's; combines with --device-core "
-                    "and --device-counts, and the proofs are the same bytes")
-    ap.add_argument("--device-counts", action="store_true", help="core shards: count the Byte, Range and Program multiplicities on the device from "
-                    "the tables that are proved (riscv_exec.device_lookup_tables) instead of taking the tracer's three main tables; with or "
-                    "without --device-core, and the proofs are the same bytes")
     ap.add_argument("--device-shard", action="store_true", help="core, memory, Keccak and secp256k1 shards: make the WHOLE shard on the device "
-                    "from the executor's records (riscv_exec.device_core_shard: the event partition kernel, every chip's table, the public "
+                    "from the executor's records (riscv_exec.device_shard over run_records — device_core_shard: the event partition kernel, every chip's table, the public "
                     "values' Global fields, the lookup counts; device_memory_shard: MemoryGlobalInit / Finalize from the run's address lists; "
                     "device_precompile_shard: the wide tables, SyscallPrecompile, MemoryLocal from the calls' event records) — no tracer and "
                     "no host table is built for them; the public values are chained by the previous shard's, the Global events still join "
@@ -156,31 +140,18 @@ def main():
     shards, gevs, kept, cycles, last, resident, pvs, pk, pk_prep, warmed = [], [], {}, 0, None, [], [], None, None, {}
     t_all = time.perf_counter()
     t_prev = t_all
-    keccak_events = [] if args.device_keccak and not args.dry_run else None
-    secp_events = [] if args.device_secp and not args.dry_run else None
-    gen = X.program_shards(ex, shard_cycles, device=device, core_limit=args.core_shards or None, keccak_events=keccak_events,
-                           secp_events=secp_events, untraced_core=args.device_shard, untraced_memory=args.device_shard,
-                           untraced_precompile=set(X.DEVICE_PRECOMPILE_KINDS) if args.device_shard else ())
-    while True:
-        try:
-            kind, machine, tabs, publics, gev, sh = next(gen)
-        except StopIteration:
-            break
-        device_chips = None
-        if args.device_shard and kind == "core":                        # untraced: the publics slot holds the previous shard's public values
+    for rec in X.run_records(ex, shard_cycles, core_limit=args.core_shards or None):
+        kind, sh, tabs, device_chips = rec.kind, rec.executed, None, None
+        if args.device_shard and kind in X.DEVICE_KINDS:                # no tracer and no host table for these
             if pk_prep is None:
                 pk_prep = {n: to_col_major(t) for n, t in X.preprocessed_tables(ex, "cuda").items()}
-            machine, device_chips, publics, gev9 = X.device_core_shard(ex, sh, pk_prep, prev=publics)
+            machine, device_chips, publics, gev9 = X.device_shard(ex, rec, pk_prep)
             gev = X.global_events_11(gev9)
-        elif args.device_shard and kind == "memory":                    # untraced: the run's context, then device_memory_shard's arguments
-            machine, device_chips, publics, gev9 = X.device_memory_shard(*sh[:4], pk_prep, publics, previous_init=sh[4], previous_fin=sh[5])
-            gev, sh = X.global_events_11(gev9), None
-        elif args.device_shard and kind in X.DEVICE_PRECOMPILE_KINDS:   # untraced: the run's context, then the event records
-            machine, device_chips, publics, gev9 = X.device_precompile_shard(kind, sh, pk_prep, publics)
-            gev, sh = X.global_events_11(gev9), None
+        else:
+            machine, tabs, publics, gev = X.host_shard(ex, rec, device)
         if device == "cuda":
             torch.cuda.synchronize()
-        t_build = time.perf_counter() - t_prev                          # executor + tables of this shard (the generator ran both)
+        t_build = time.perf_counter() - t_prev                          # executor (inside run_records) + tables of this shard
         heights = {c[0].name: c[2].height for c in device_chips} if device_chips is not None else {a.name: int(tabs[a.name][1].shape[0]) for a, _ in machine}
         area = sum(heights[a.name] * (a.main_width + a.prep_width) for a, _ in machine)
         row = {"kind": kind, "chips": len(machine), "cells": area, "build_s": round(t_build, 3),
@@ -216,37 +187,6 @@ def main():
             else:
                 assert sorted(a.name for a, _ in machine if tabs[a.name][0] is not None) == sorted(pk_prep), "a shard without the program's preprocessed chips"
                 chips = [(a, i, to_col_major(tabs[a.name][1]), pk_prep.get(a.name)) for a, i in machine]
-            if keccak_events is not None and kind == "keccak" and device_chips is None:
-                from sp1_amd.machines import riscv_more_trace as MT
-                names = ("KeccakPermute", "KeccakPermuteControl")
-                made = dict(zip(names, MT.keccak_device_tables(keccak_events.pop(), [int(tabs[n][1].shape[0]) for n in names])))
-                chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
-                row["device_keccak"] = True
-            if secp_events is not None and kind in ("secp256k1_add", "secp256k1_double") and device_chips is None:
-                from sp1_amd.machines import riscv_more_trace as MT
-                name, events = secp_events.pop()
-                assert name == kind
-                chip = MT.SECP256K1_CHIPS[kind[len("secp256k1_"):]]
-                made = {chip: MT.secp256k1_device_table(kind[len("secp256k1_"):], events, int(tabs[chip][1].shape[0]))}
-                chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
-                row["device_secp"] = True
-            if args.device_core and kind == "core" and device_chips is None:
-                made = X.core_device_tables(sh.events, {a.name: int(tabs[a.name][1].shape[0]) for a, _ in machine})
-                chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
-                row["device_core"], row["device_core_chips"] = True, len(made)
-            if args.device_rest and kind == "core" and device_chips is None:
-                heights = {a.name: int(tabs[a.name][1].shape[0]) for a, _ in machine}
-                made, (g_count, g_digest) = X.core_device_tables_rest(sh, heights, syscall_global_events=gev[2 * len(sh.local):])
-                assert g_count == PVM.get(publics, "global_count") and g_digest == PVM.get(publics, "global_cumulative_sum"), \
-                    "the device-made Global table accumulates to another digest than the shard's public values"
-                chips = [(a, i, made.get(a.name, m), p) for a, i, m, p in chips]
-                row["device_rest"], row["device_rest_chips"] = True, sorted(made)
-            if args.device_counts and kind == "core" and device_chips is None:
-                pc_base, program = ex.program()
-                counted = X.device_lookup_tables(machine, {a.name: (m, p) for a, _, m, p in chips if a.name not in ("Byte", "Range", "Program")},
-                                                 publics, sh.events, program, pc_base)
-                chips = [(a, i, counted.get(a.name, m), p) for a, i, m, p in chips]
-                row["device_counts"] = True
             if tabs is not None:
                 tabs.clear()
             pv = RT.to_monty_np(publics)

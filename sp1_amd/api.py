@@ -563,13 +563,7 @@ def tracegen_riscv_alu(chip, events, height, stream=None):
     """`generate_trace_device` for one of the RISC-V instruction chips of RISCV_ALU_CHIPS (sp1hip_tracegen_riscv_alu): events = a
     device int64 tensor [n, 11] of sp1hip_rv64_alu_event_t records (riscv_exec.pack_alu_events); returns the column-major table
     [width][height] as a ColMajor."""
-    kind = RISCV_ALU_CHIPS[chip]
-    width = _L().sp1hip_tracegen_riscv_alu_width(kind)
-    n = int(events.shape[0])
-    assert events.dtype == torch.int64 and (n == 0 or (events.shape[1] == ALU_EVENT_WORDS and events.is_contiguous()))
-    out = device_words(width * int(height))
-    check(_L().sp1hip_tracegen_riscv_alu(kind, _dptr(out), int(height), _dptr(events) if n else None, n, _stream_ptr(stream)))
-    return ColMajor(out, int(height), width)
+    return _tracegen_records("sp1hip_tracegen_riscv_alu", ALU_EVENT_WORDS, RISCV_ALU_CHIPS[chip], events, height, stream)
 
 
 RISCV_MEM_CHIPS = {"LoadByte": 0, "LoadHalf": 1, "LoadWord": 2, "LoadDouble": 3, "LoadX0": 4,                     # SP1HIP_RV64_MEM_CHIP_*
@@ -581,21 +575,18 @@ def tracegen_riscv_mem(chip, events, height, stream=None):
     """`generate_trace_device` for one of the load and store chips of RISCV_MEM_CHIPS (sp1hip_tracegen_riscv_mem): events = a
     device int64 tensor [n, 12] of sp1hip_rv64_mem_event_t records (riscv_exec.pack_mem_events); returns the column-major table
     [width][height] as a ColMajor."""
-    kind = RISCV_MEM_CHIPS[chip]
-    width = _L().sp1hip_tracegen_riscv_mem_width(kind)
-    n = int(events.shape[0])
-    assert events.dtype == torch.int64 and (n == 0 or (events.shape[1] == MEM_EVENT_WORDS and events.is_contiguous()))
-    out = device_words(width * int(height))
-    check(_L().sp1hip_tracegen_riscv_mem(kind, _dptr(out), int(height), _dptr(events) if n else None, n, _stream_ptr(stream)))
-    return ColMajor(out, int(height), width)
+    return _tracegen_records("sp1hip_tracegen_riscv_mem", MEM_EVENT_WORDS, RISCV_MEM_CHIPS[chip], events, height, stream)
 
 
-def _tracegen_alu_records(fn, events, height, stream):
-    width = getattr(_L(), fn + "_width")()
+def _tracegen_records(fn, words, kind, events, height, stream):
+    """The body of every wrapper whose entry point makes one table from one stream of fixed-size records: `fn` the entry point
+    (its width query is fn + "_width"), `words` the record's u64 words, `kind` the leading chip argument of both or None."""
+    lead = () if kind is None else (kind,)
+    width = getattr(_L(), fn + "_width")(*lead)
     n = int(events.shape[0])
-    assert events.dtype == torch.int64 and (n == 0 or (events.is_cuda and events.shape[1] == ALU_EVENT_WORDS and events.is_contiguous()))
+    assert events.dtype == torch.int64 and (n == 0 or (events.is_cuda and events.shape[1] == words and events.is_contiguous()))
     out = device_words(width * int(height))
-    check(getattr(_L(), fn)(_dptr(out), int(height), _dptr(events) if n else None, n, _stream_ptr(stream)))
+    check(getattr(_L(), fn)(*lead, _dptr(out), int(height), _dptr(events) if n else None, n, _stream_ptr(stream)))
     return ColMajor(out, int(height), width)
 
 
@@ -603,13 +594,13 @@ def tracegen_riscv_divrem(events, height, stream=None):
     """`generate_trace_device` for the DivRem chip (sp1hip_tracegen_riscv_divrem): events = a device int64 tensor [n, 11] of
     sp1hip_rv64_alu_event_t records (riscv_exec.pack_alu_events(events, "DivRem")); returns the column-major [246][height] table as
     a ColMajor, rows >= n the reference's "0 / 1" padding row."""
-    return _tracegen_alu_records("sp1hip_tracegen_riscv_divrem", events, height, stream)
+    return tracegen_riscv_records("DivRem", events, height, stream)
 
 
 def tracegen_riscv_alu_x0(events, height, stream=None):
     """The same for the AluX0 chip (sp1hip_tracegen_riscv_alu_x0; pack_alu_events(events, "AluX0")): column-major [34][height],
     zero padding rows."""
-    return _tracegen_alu_records("sp1hip_tracegen_riscv_alu_x0", events, height, stream)
+    return tracegen_riscv_records("AluX0", events, height, stream)
 
 
 MEMORY_LOCAL_RECORD_WORDS, MEMORY_LOCAL_WIDTH, GLOBAL_EVENT_WORDS = 5, 20, 9
@@ -737,7 +728,7 @@ def tracegen_riscv_syscall_instrs(events, height, stream=None):
     """`generate_trace_device` for the SyscallInstrs chip (sp1hip_tracegen_riscv_syscall_instrs): events = a device int64 tensor [n, 11]
     of the ECALLs' sp1hip_rv64_alu_event_t records (bin "SyscallInstrs" of partition_rv64_events); returns the column-major
     [65][height] table as a ColMajor, zero padding rows."""
-    return _tracegen_alu_records("sp1hip_tracegen_riscv_syscall_instrs", events, height, stream)
+    return tracegen_riscv_records("SyscallInstrs", events, height, stream)
 
 
 def tracegen_riscv_syscall_core(events, height, global_events=None, stream=None):
@@ -755,75 +746,70 @@ def tracegen_riscv_syscall_core(events, height, global_events=None, stream=None)
     return ColMajor(out, int(height), width)
 
 
-def _tracegen_bump(fn, records, height, stream):
-    width = getattr(_L(), fn + "_width")()
-    n = int(records.shape[0])
-    assert records.dtype == torch.int64 and (n == 0 or (records.is_cuda and records.shape[1] == 4 and records.is_contiguous()))
-    out = device_words(width * int(height))
-    check(getattr(_L(), fn)(_dptr(out), int(height), _dptr(records) if n else None, n, _stream_ptr(stream)))
-    return ColMajor(out, int(height), width)
+BUMP_RECORD_WORDS = 4                                                               # the StateBump / MemoryBump bins' records
 
 
 def tracegen_riscv_state_bump(records, height, stream=None):
     """`generate_trace_device` for the StateBump chip (sp1hip_tracegen_riscv_state_bump): records = a device int64 tensor [n, 4] (clk, pc,
     next_pc, clock step | pc_carry << 32: bin "StateBump"); column-major [14][height], zero padding rows."""
-    return _tracegen_bump("sp1hip_tracegen_riscv_state_bump", records, height, stream)
+    return tracegen_riscv_records("StateBump", records, height, stream)
 
 
 def tracegen_riscv_memory_bump(records, height, stream=None):
     """The same for the MemoryBump chip (records: register, previous timestamp, value, window start — bin "MemoryBump"):
     column-major [15][height]."""
-    return _tracegen_bump("sp1hip_tracegen_riscv_memory_bump", records, height, stream)
+    return tracegen_riscv_records("MemoryBump", records, height, stream)
 
 
 KECCAK_EVENT_WORDS = 77                                                            # SP1HIP_RV64_KECCAK_WORDS
-
-
-def _tracegen_keccak(fn, events, height, stream):
-    width = getattr(_L(), fn + "_width")()
-    n = int(events.shape[0])
-    assert events.dtype == torch.int64 and (n == 0 or (events.is_cuda and events.shape[1] == KECCAK_EVENT_WORDS and events.is_contiguous()))
-    out = device_words(width * int(height))
-    check(getattr(_L(), fn)(_dptr(out), int(height), _dptr(events) if n else None, n, _stream_ptr(stream)))
-    return ColMajor(out, int(height), width)
 
 
 def tracegen_riscv_keccak(events, height, stream=None):
     """`generate_trace_device` for the KeccakPermute chip (sp1hip_tracegen_riscv_keccak): events = a device int64 tensor [n, 77]
     of the executor's KECCAK_PERMUTE records (riscv_exec.ExecutedShard.keccak); 24 rows per event, height >= 24 n. Returns the
     column-major [2640][height] table as a ColMajor."""
-    return _tracegen_keccak("sp1hip_tracegen_riscv_keccak", events, height, stream)
+    return tracegen_riscv_records("KeccakPermute", events, height, stream)
 
 
 def tracegen_riscv_keccak_control(events, height, stream=None):
     """The same events' KeccakPermuteControl table (sp1hip_tracegen_riscv_keccak_control): one row per event, height >= n;
     column-major [634][height]."""
-    return _tracegen_keccak("sp1hip_tracegen_riscv_keccak_control", events, height, stream)
+    return tracegen_riscv_records("KeccakPermuteControl", events, height, stream)
 
 
 SECP_ADD_EVENT_WORDS, SECP_DOUBLE_EVENT_WORDS = 43, 26                              # SP1HIP_RV64_SECP_ADD_WORDS, _DOUBLE_WORDS
-
-
-def _tracegen_secp(fn, words, events, height, stream):
-    width = getattr(_L(), fn + "_width")()
-    n = int(events.shape[0])
-    assert events.dtype == torch.int64 and (n == 0 or (events.is_cuda and events.shape[1] == words and events.is_contiguous()))
-    out = device_words(width * int(height))
-    check(getattr(_L(), fn)(_dptr(out), int(height), _dptr(events) if n else None, n, _stream_ptr(stream)))
-    return ColMajor(out, int(height), width)
 
 
 def tracegen_riscv_secp256k1_add(events, height, stream=None):
     """`generate_trace_device` for the Secp256k1AddAssign chip (sp1hip_tracegen_riscv_secp256k1_add): events = a device int64 tensor
     [n, 43] of the executor's SECP256K1_ADD records (riscv_exec.ExecutedShard.secp256k1_add); one row per event, height >= n,
     padding rows = the reference's dummy row. Returns the column-major [1599][height] table as a ColMajor."""
-    return _tracegen_secp("sp1hip_tracegen_riscv_secp256k1_add", SECP_ADD_EVENT_WORDS, events, height, stream)
+    return tracegen_riscv_records("Secp256k1AddAssign", events, height, stream)
 
 
 def tracegen_riscv_secp256k1_double(events, height, stream=None):
     """The same for the Secp256k1DoubleAssign chip (sp1hip_tracegen_riscv_secp256k1_double): events int64 [n, 26]
     (ExecutedShard.secp256k1_double); column-major [1591][height]."""
-    return _tracegen_secp("sp1hip_tracegen_riscv_secp256k1_double", SECP_DOUBLE_EVENT_WORDS, events, height, stream)
+    return tracegen_riscv_records("Secp256k1DoubleAssign", events, height, stream)
+
+
+# chip: (entry point, u64 words of a record, leading chip argument or None) — every chip whose table is made from its record stream
+# alone, the wrappers above by chip name (MemoryLocal, MemoryGlobal*, SyscallCore and SyscallPrecompile also write Global events)
+RISCV_TRACEGEN = {**{c: ("sp1hip_tracegen_riscv_alu", ALU_EVENT_WORDS, k) for c, k in RISCV_ALU_CHIPS.items()},
+                  **{c: ("sp1hip_tracegen_riscv_mem", MEM_EVENT_WORDS, k) for c, k in RISCV_MEM_CHIPS.items()},
+                  "DivRem": ("sp1hip_tracegen_riscv_divrem", ALU_EVENT_WORDS, None), "AluX0": ("sp1hip_tracegen_riscv_alu_x0", ALU_EVENT_WORDS, None),
+                  "SyscallInstrs": ("sp1hip_tracegen_riscv_syscall_instrs", ALU_EVENT_WORDS, None),
+                  "StateBump": ("sp1hip_tracegen_riscv_state_bump", BUMP_RECORD_WORDS, None),
+                  "MemoryBump": ("sp1hip_tracegen_riscv_memory_bump", BUMP_RECORD_WORDS, None),
+                  "KeccakPermute": ("sp1hip_tracegen_riscv_keccak", KECCAK_EVENT_WORDS, None),
+                  "KeccakPermuteControl": ("sp1hip_tracegen_riscv_keccak_control", KECCAK_EVENT_WORDS, None),
+                  "Secp256k1AddAssign": ("sp1hip_tracegen_riscv_secp256k1_add", SECP_ADD_EVENT_WORDS, None),
+                  "Secp256k1DoubleAssign": ("sp1hip_tracegen_riscv_secp256k1_double", SECP_DOUBLE_EVENT_WORDS, None)}
+
+
+def tracegen_riscv_records(chip, records, height, stream=None):
+    """The table of a chip of RISCV_TRACEGEN from its record stream (a device int64 tensor [n, words]): the wrapper of that chip."""
+    return _tracegen_records(*RISCV_TRACEGEN[chip], records, height, stream)
 
 
 class LookupCounter:

@@ -6,6 +6,8 @@ riscv_trace.py, whose column fillers this module drives with executed events ins
     ex = Executor(open(elf, "rb").read(), stdin=[n.to_bytes(4, "little")])
     for shard in ex.shards(max_cycles=1 << 21):               # ExecutedShard: events, local memory, public values
         machine, tables, publics = shard_tables(ex, shard, device)   # every chip's (prep, main), ready for api.prove_shard
+    for rec in run_records(ex, max_cycles=1 << 21):           # ShardRecords: every shard of the run — core, precompile, memory — cut once
+        machine, tables, publics, gev = host_shard(ex, rec)   # ... or device_shard(ex, rec, prep): every table made on the device
 
 The proof statement per shard is the reference's: the chips of the shard's shape cluster (those without events at height zero),
 their constraints on every row, and the Byte / Range / Program / Memory / State buses balanced against the messages the shard's
@@ -14,6 +16,8 @@ accumulation and of the memory-initialisation chains); what crosses shards (memo
 digest, and the public values chain from shard to shard as `SP1Prover::verify` requires (public_values.verify_proof_public_values).
 """
 import ctypes as C
+import dataclasses
+import functools
 import gzip
 import os
 import types
@@ -30,6 +34,7 @@ from .riscv_trace import I64, MASK16, OPC, P, POS_OFF, Table, limbs16
 
 EV_WORDS, KECCAK_WORDS, POSEIDON2_WORDS, SHA_EXTEND_WORDS, SHA_COMPRESS_WORDS, UINT256_WORDS = 20, 77, 26, 786, 155, 31
 SECP_ADD_WORDS, SECP_DOUBLE_WORDS = 43, 26
+PRECOMPILE_KINDS = ("keccak", "poseidon2", "sha_extend", "sha_compress", "uint256", "secp256k1_add", "secp256k1_double")   # ExecutedShard's attributes
 # kind: (SP1HIP_RV64_FAMILY_*, chip) — the field / curve precompiles behind sp1hip_rv64_precompile_events (include/sp1hip.h)
 FAMILIES = {"secp256r1_add": (0, "Secp256r1AddAssign"), "secp256r1_double": (1, "Secp256r1DoubleAssign"), "bn254_add": (2, "Bn254AddAssign"),
             "bn254_double": (3, "Bn254DoubleAssign"), "bls12381_add": (4, "Bls12381AddAssign"), "bls12381_double": (5, "Bls12381DoubleAssign"),
@@ -67,6 +72,11 @@ class ExecutedShard:
         self.committed_value_digest = [int(x) for x in info.committed_value_digest]
         self.deferred_proofs_digest = [int(x) for x in info.deferred_proofs_digest]
         self.estimated_area, self.estimated_max_height = int(info.estimated_area), int(info.estimated_max_height)
+
+    def precompile_events(self):
+        """{kind: events} of the shard's precompile calls, only the kinds that occurred: the seven named attributes, then `families`."""
+        named = {kind: getattr(self, kind) for kind in PRECOMPILE_KINDS}
+        return {kind: events for kind, events in {**named, **self.families}.items() if events.shape[0]}
 
 
 class Executor:
@@ -473,21 +483,40 @@ def _core_device_tables_rest(shard, heights, syscall_global_events, stream):
             packed = torch.as_tensor(np.ascontiguousarray(packed)).cuda()
         out[name] = gen(packed, int(heights[name]), stream=stream)
     m = 0 if syscall_global_events is None else int(syscall_global_events.shape[0])
-    local = torch.as_tensor(shard.local).reshape(-1, 5)
-    local = (local if local.is_cuda else local.cuda()).contiguous()
-    count = 2 * int(local.shape[0]) + m
-    digest = global_digest(None, 0)
-    if heights.get("MemoryLocal"):
-        out["MemoryLocal"], gev = api.tracegen_riscv_memory_local(local, int(heights["MemoryLocal"]), extra_global_events=m, stream=stream)
-    if heights.get("Global"):
-        assert "MemoryLocal" in out or not local.shape[0], "the Global table needs the MemoryLocal table's events"
-        if "MemoryLocal" not in out:
-            gev = torch.zeros((m, api.GLOBAL_EVENT_WORDS), dtype=torch.int32, device="cuda")
-        if m:
-            gev[count - m:] = global_events_9(torch.as_tensor(syscall_global_events)).to(gev.device)
-        out["Global"] = api.tracegen_riscv_global(gev, int(heights["Global"]), stream=stream)
-        digest = global_digest(out["Global"], count)
+    _, count, digest = _local_and_global_tables(out, _on_device(shard.local, 5), m, stream, heights, fill=lambda tail: tail.copy_(
+        global_events_9(torch.as_tensor(syscall_global_events)).to(tail.device)))
     return out, (count, digest)
+
+
+def _on_device(records, words):
+    """The executor's records (numpy or torch, anywhere) as a contiguous device tensor [n, words], uploaded as they are."""
+    t = torch.as_tensor(np.ascontiguousarray(records) if isinstance(records, np.ndarray) else records).reshape(-1, words)
+    return (t if t.is_cuda else t.cuda()).contiguous()
+
+
+def _local_and_global_tables(made, local, extra, stream, heights=None, fill=None, pv=None):
+    """What every device builder has in its middle: made["MemoryLocal"] from `local` (device int64 [n, 5]); the caller's `extra`
+    events in the tail of MemoryLocal's Global events, written by fill(tail); made["Global"] from all of them; the Global table's
+    count and digest, set in the public values `pv` if given. Returns (global events, count, digest). `heights`: None for pad32 of
+    each table's rows, or {name: rows} — a table without an entry is not made (core_device_tables_rest)."""
+    from .. import api
+    n_local = int(local.shape[0])
+    count = 2 * n_local + extra
+    rows = lambda name, n: RT.pad32(n) if heights is None else int(heights.get(name) or 0)
+    gev, digest = None, global_digest(None, 0)
+    if heights is None or rows("MemoryLocal", n_local):
+        made["MemoryLocal"], gev = api.tracegen_riscv_memory_local(local, rows("MemoryLocal", n_local), extra_global_events=extra, stream=stream)
+    if heights is None or rows("Global", count):
+        assert gev is not None or not n_local, "the Global table needs the MemoryLocal table's events"
+        if gev is None:
+            gev = torch.zeros((extra, api.GLOBAL_EVENT_WORDS), dtype=torch.int32, device="cuda")
+        if extra:
+            fill(gev[2 * n_local:])
+        made["Global"] = api.tracegen_riscv_global(gev, rows("Global", count), stream=stream)
+        digest = global_digest(made["Global"], count)
+    if pv is not None:
+        PVM.set_global(pv, count, digest)
+    return gev, count, digest
 
 
 def device_lookup_tables(machine, tables, publics, shard_events, program, pc_base, stream=None):
@@ -548,48 +577,23 @@ def device_core_shard(executor, shard, prep, prev=None, stream=None):
     where the host tracer's stand chip by chip."""
     from .. import api
     with torch.cuda.stream(stream or torch.cuda.current_stream()):
-        events = torch.as_tensor(shard.events).reshape(-1, EV_WORDS)
-        events = (events if events.is_cuda else events.cuda()).contiguous()
-        local = torch.as_tensor(shard.local).reshape(-1, 5)
-        local = (local if local.is_cuda else local.cuda()).contiguous()
+        events, local = _on_device(shard.events, EV_WORDS), _on_device(shard.local, 5)
         parts = api.partition_rv64_events(events, stream=stream)
-        made = {}
-        for name, rec in parts.items():
-            n = int(rec.shape[0])
-            if n == 0 or name == "SyscallCore":
-                continue
-            height = RT.pad32(n)
-            if name in api.RISCV_ALU_CHIPS:
-                made[name] = api.tracegen_riscv_alu(name, rec, height, stream=stream)
-            elif name in api.RISCV_MEM_CHIPS:
-                made[name] = api.tracegen_riscv_mem(name, rec, height, stream=stream)
-            else:
-                gen = {"DivRem": api.tracegen_riscv_divrem, "AluX0": api.tracegen_riscv_alu_x0, "SyscallInstrs": api.tracegen_riscv_syscall_instrs,
-                       "StateBump": api.tracegen_riscv_state_bump, "MemoryBump": api.tracegen_riscv_memory_bump}[name]
-                made[name] = gen(rec, height, stream=stream)
-        n_local, m = int(local.shape[0]), int(parts["SyscallCore"].shape[0])
-        count = 2 * n_local + m
-        made["MemoryLocal"], gev = api.tracegen_riscv_memory_local(local, RT.pad32(n_local), extra_global_events=m, stream=stream)
-        if m:
-            made["SyscallCore"] = api.tracegen_riscv_syscall_core(parts["SyscallCore"], RT.pad32(m), global_events=gev[2 * n_local:], stream=stream)
-        made["Global"] = api.tracegen_riscv_global(gev, RT.pad32(count), stream=stream)
-        pv = execution_public_values(shard, prev)
-        PVM.set_global(pv, count, global_digest(made["Global"], count))
+        syscalls = parts.pop("SyscallCore")                  # made behind MemoryLocal: its Global events go into the tail of MemoryLocal's
+        made = {name: api.tracegen_riscv_records(name, rec, RT.pad32(int(rec.shape[0])), stream=stream) for name, rec in parts.items() if rec.shape[0]}
+        m, pv = int(syscalls.shape[0]), execution_public_values(shard, prev)
+        gev, _, _ = _local_and_global_tables(made, local, m, stream, pv=pv, fill=lambda tail: made.update(
+            SyscallCore=api.tracegen_riscv_syscall_core(syscalls, RT.pad32(m), global_events=tail, stream=stream)))
         publics = PVM.to_tensor(pv)
-        names = sorted(RT.smallest_cluster(set(made) | set(prep)))
-        machine = [R.chip(n) for n in names]
-        for a, _ in machine:
-            if a.name not in made and a.name not in prep:
-                assert a.prep_width == 0, a.name
-                made[a.name] = api.ColMajor(api.device_words(0), 0, a.main_width)
         pc_base, program = executor.program()
-        made.update(device_lookup_tables(machine, {n: (t, prep.get(n)) for n, t in made.items()}, publics, events, program, pc_base, stream=stream))
-        return machine, [(a, it, made[a.name], prep.get(a.name)) for a, it in machine], publics, gev
+        machine, chips = _close_device_shard(made, prep, RT.smallest_cluster(set(made) | set(prep)), publics, RT.RunContext(program, pc_base), stream, events)
+        return machine, chips, publics, gev
 
 
-def _close_device_shard(made, prep, cluster, publics, ctx, stream):
-    """What device_memory_shard and device_precompile_shard end with: the cluster's chips without rows at height zero, the Byte /
-    Range / Program counts (device_lookup_tables; the shard executes nothing), the chips in name order."""
+def _close_device_shard(made, prep, cluster, publics, ctx, stream, shard_events=None):
+    """What every device builder ends with: the cluster's chips without rows at height zero, the Byte / Range / Program counts
+    (device_lookup_tables; `shard_events`: a core shard's executed instructions, None for a shard that executes nothing), the chips
+    in name order."""
     from .. import api
     names = sorted(cluster)
     machine = [R.chip(n) for n in names]
@@ -597,7 +601,7 @@ def _close_device_shard(made, prep, cluster, publics, ctx, stream):
         if a.name not in made and a.name not in prep:
             assert a.prep_width == 0, a.name
             made[a.name] = api.ColMajor(api.device_words(0), 0, a.main_width)
-    made.update(device_lookup_tables(machine, {n: (t, prep.get(n)) for n, t in made.items()}, publics, None, ctx.program, ctx.pc_base, stream=stream))
+    made.update(device_lookup_tables(machine, {n: (t, prep.get(n)) for n, t in made.items()}, publics, shard_events, ctx.program, ctx.pc_base, stream=stream))
     return machine, [(a, it, made[a.name], prep.get(a.name)) for a, it in machine]
 
 
@@ -667,28 +671,36 @@ def device_precompile_shard(kind, events, prep, ctx, stream=None):
     initial state with the Global fields set. No Tracer, no host table."""
     from .. import api
     words, syscall_id, arg2_word, segments = api.PRECOMPILE_DESCRIPTORS[kind]
+    chip, control, rows_per_call, _ = PRECOMPILES[kind]
     with torch.cuda.stream(stream or torch.cuda.current_stream()):
-        ev = torch.as_tensor(np.ascontiguousarray(events) if isinstance(events, np.ndarray) else events).reshape(-1, words)
-        ev = (ev if ev.is_cuda else ev.cuda()).contiguous()
+        ev = _on_device(events, words)
         n = int(ev.shape[0])
         assert n, "a precompile shard has at least one call"
-        if kind == "keccak":
-            made = {"KeccakPermute": api.tracegen_riscv_keccak(ev, RT.pad32(24 * n), stream=stream), "KeccakPermuteControl": api.tracegen_riscv_keccak_control(ev, RT.pad32(n), stream=stream)}
-        elif kind == "secp256k1_add":
-            made = {"Secp256k1AddAssign": api.tracegen_riscv_secp256k1_add(ev, RT.pad32(n), stream=stream)}
-        else:
-            made = {"Secp256k1DoubleAssign": api.tracegen_riscv_secp256k1_double(ev, RT.pad32(n), stream=stream)}
-        local = api.precompile_local_records(ev, segments, stream=stream)
-        n_local = int(local.shape[0])
-        count = 2 * n_local + n
-        made["MemoryLocal"], gev = api.tracegen_riscv_memory_local(local, RT.pad32(n_local), extra_global_events=n, stream=stream)
-        made["SyscallPrecompile"] = api.tracegen_riscv_syscall_precompile(ev, RT.pad32(n), syscall_id, arg2_word, global_events=gev[2 * n_local:], stream=stream)
-        made["Global"] = api.tracegen_riscv_global(gev, RT.pad32(count), stream=stream)
+        made = {chip: api.tracegen_riscv_records(chip, ev, RT.pad32(rows_per_call * n), stream=stream)}
+        if control:
+            made[control] = api.tracegen_riscv_records(control, ev, RT.pad32(n), stream=stream)
         pv = PVM.no_memory_events(PVM.initialized_state(ctx.pc_start))
-        PVM.set_global(pv, count, global_digest(made["Global"], count))
+        gev, _, _ = _local_and_global_tables(made, api.precompile_local_records(ev, segments, stream=stream), n, stream, pv=pv, fill=lambda tail: made.update(
+            SyscallPrecompile=api.tracegen_riscv_syscall_precompile(ev, RT.pad32(n), syscall_id, arg2_word, global_events=tail, stream=stream)))
         publics = PVM.to_tensor(pv)
         machine, chips = _close_device_shard(made, prep, RT.smallest_cluster(set(made) | set(prep)), publics, ctx, stream)
         return machine, chips, publics, gev
+
+
+DEVICE_KINDS = ("core", "memory") + DEVICE_PRECOMPILE_KINDS
+
+
+def device_shard(executor, rec, prep, stream=None):
+    """One shard of a run (`rec`: a ShardRecords of run_records, its kind one of DEVICE_KINDS) made ON THE DEVICE by the builder of
+    its kind — device_core_shard, device_memory_shard or device_precompile_shard: (machine, chips, publics, global events [count, 9])."""
+    if rec.kind == "core":
+        return device_core_shard(executor, rec.executed, prep, prev=rec.prev, stream=stream)
+    if rec.kind == "memory":
+        return device_memory_shard(rec.init_addrs, rec.init_recs, rec.fin_addrs, rec.fin_recs, prep, rec.ctx, previous_init=rec.previous_init,
+                                   previous_fin=rec.previous_fin, stream=stream)
+    if rec.kind in DEVICE_PRECOMPILE_KINDS:
+        return device_precompile_shard(rec.kind, rec.events, prep, rec.ctx, stream=stream)
+    raise ValueError("no device builder for a %r shard: device_shard makes %s" % (rec.kind, ", ".join(DEVICE_KINDS)))
 
 
 def execution_public_values(sh, prev=None):
@@ -771,99 +783,51 @@ def split_thresholds(program_rows):
     return SplitThresholds(program_rows)
 
 
-def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_events=None, secp_events=None, untraced_core=False,
-                   untraced_memory=False, untraced_precompile=()):
-    """Every shard of a run, in the order the reference's controller emits them: the core shards as the program executes
-    (`(kind, machine, tables, publics, global events, ExecutedShard)` with kind = "core"), then one precompile shard for the
-    KECCAK_PERMUTE, POSEIDON2, SHA_EXTEND and SHA_COMPRESS calls each if there were any ("keccak", "poseidon2", "sha_extend",
-    "sha_compress"), then the memory shard: MemoryGlobalInit / MemoryGlobalFinalize over
-    every address the run touched ("memory"). The global events of all shards cancel as a multiset: that is the statement the
-    shards' septic-curve digests add up to. `core_limit`: only the first so many core shards are traced and yielded (the rest of
-    the program still runs, so every precompile and memory shard is there). `keccak_events` / `secp_events`: a list that takes,
-    per Keccak / secp256k1 shard yielded, the shard's event records (for secp256k1 a pair (kind, events)) — what device trace
-    generation makes the chip's table from. `untraced_core`: the core shards are yielded UNTRACED — `("core", None, None, prev, None,
-    ExecutedShard)` with prev = the previous core shard's public-value words (None for the first) — for device_core_shard, which
-    makes machine, tables, public values and global events on the device; no EventTracer is built for them. `untraced_precompile`: a
-    set of kinds of DEVICE_PRECOMPILE_KINDS whose shards are yielded UNTRACED — `(kind, None, None, RunContext, None, events)` with
-    events = the shard's event records, an int64 array [n, 77 / 43 / 26] — for device_precompile_shard(kind, events, prep, ctx).
-    `untraced_memory`: the memory shards are yielded UNTRACED — `("memory", None, None, RunContext, None, (init_addrs, init_recs,
-    fin_addrs, fin_recs, previous_init, previous_fin))`, the arguments of device_memory_shard in its order (the RunContext holds the
-    run's final state); the two address chains are still threaded here. No Tracer is built for either."""
-    from . import riscv_more_trace as MT
-    keccak, poseidon2, sha_extend, sha_compress, uint256, secp_add, secp_double = [], [], [], [], [], [], []
-    families = {}
-    n_core = 0
-    prev_pv, ctx, shard = None, None, None
+@dataclasses.dataclass
+class ShardRecords:
+    """One shard of a run as run_records cuts it: the executor's records of its `kind` and the run's RunContext, no table. A core
+    shard has `executed` (the ExecutedShard) and `prev` (the previous core shard's execution_public_values, None for the first); a
+    precompile shard `events` (its chunk of the kind's int64 records, as the executor left them); a memory shard the address lists
+    and the two chains' previous addresses — the arguments of riscv_more_trace.memory_shard_from and device_memory_shard."""
+    kind: str
+    ctx: RT.RunContext
+    executed: ExecutedShard = None
+    prev: list = None
+    events: np.ndarray = None
+    init_addrs: np.ndarray = None
+    init_recs: np.ndarray = None
+    fin_addrs: np.ndarray = None
+    fin_recs: np.ndarray = None
+    previous_init: int = 0
+    previous_fin: int = 0
+
+
+def run_records(executor, max_cycles, core_limit=None):
+    """Every shard of a run as a ShardRecords, in the order the reference's controller emits them: the core shards as the program
+    executes, then the precompile shards — every kind's calls of the whole run, cut at the `SplitOpts` thresholds (split_thresholds),
+    the kinds in the order of PRECOMPILE_KINDS, then FAMILIES —, then the memory shards: MemoryGlobalInit / MemoryGlobalFinalize over
+    every address the run touched. `core_limit`: only the first so many core shards are recorded and yielded (the rest of the program
+    still runs, so every precompile and memory shard is there). No table is made and no device is touched: host_shard or
+    device_shard makes a record's tables."""
+    calls, n_core, prev, ctx, shard = {}, 0, None, None, None
     while not executor.halted:
-        keep = core_limit is None or n_core < core_limit     # beyond the limit: executed (their precompile calls count), not traced
+        keep = core_limit is None or n_core < core_limit     # beyond the limit: executed (their precompile calls count), not recorded
         shard = executor.run_shard(max_cycles, record=keep)
         n_core += 1
         if ctx is None:                                      # what the shards without instructions take from the run (RunContext)
             pc_base, program = executor.program()
             ctx = RT.RunContext(program, pc_base, pc_start=shard.pc_start)
-        if keep and untraced_core:
-            prev_before, prev_pv = prev_pv, execution_public_values(shard, prev_pv)
-        elif keep:
-            tr = EventTracer(executor, shard, device, prev=prev_pv)
-            machine, tables, publics = tr.build()
-            prev_pv = tr.pv
-        else:
-            prev_pv = execution_public_values(shard, prev_pv)
-        if shard.keccak.shape[0]:
-            keccak.append(shard.keccak)
-        if shard.poseidon2.shape[0]:
-            poseidon2.append(shard.poseidon2)
-        if shard.sha_extend.shape[0]:
-            sha_extend.append(shard.sha_extend)
-        if shard.sha_compress.shape[0]:
-            sha_compress.append(shard.sha_compress)
-        if shard.uint256.shape[0]:
-            uint256.append(shard.uint256)
-        if shard.secp256k1_add.shape[0]:
-            secp_add.append(shard.secp256k1_add)
-        if shard.secp256k1_double.shape[0]:
-            secp_double.append(shard.secp256k1_double)
-        for kind, evs in shard.families.items():
-            families.setdefault(kind, []).append(evs)
-        if keep and untraced_core:
-            yield "core", None, None, prev_before, None, shard
-        elif keep:
-            yield "core", machine, tables, publics, tr.global_events, shard
-            del tr, machine, tables
+        for kind, events in shard.precompile_events().items():
+            calls.setdefault(kind, []).append(events)
+        if keep:
+            yield ShardRecords("core", ctx, executed=shard, prev=prev)
+        prev = execution_public_values(shard, prev)
     limit = split_thresholds(executor.program()[1].shape[0])    # (a kind's threshold is worked out when a call of that kind asks for it)
-    chunks = lambda kind, evs: (lambda a: [a[i:i + limit[kind]] for i in range(0, a.shape[0], limit[kind])])(np.concatenate(evs)) if evs else []
-    for kk in chunks("keccak", keccak):
-        if "keccak" in untraced_precompile:
-            yield "keccak", None, None, ctx, None, kk
-            continue
-        kk = torch.as_tensor(kk, device=device)
-        rd = kk[:, 2:52].reshape(-1, 25, 2)
-        machine, tables, publics, gev = MT.precompile_shard_from(kk[:, 0], kk[:, 1], rd[:, :, 1].contiguous(), rd[:, :, 0].contiguous(), device, ctx=ctx)
-        if keccak_events is not None:
-            keccak_events.append(kk)
-        yield "keccak", machine, tables, publics, gev, None
-    for pp in chunks("poseidon2", poseidon2):
-        pp = torch.as_tensor(pp, device=device)
-        rd = pp[:, 2:18].reshape(-1, 8, 2)
-        machine, tables, publics, gev = MT.poseidon2_shard_from(pp[:, 0], pp[:, 1], rd[:, :, 1].contiguous(), rd[:, :, 0].contiguous(),
-                                                               pp[:, 18:26].contiguous(), device, ctx=ctx)
-        yield "poseidon2", machine, tables, publics, gev, None
-    for name, evs, build in (("sha_extend", sha_extend, MT.sha_extend_shard_from), ("sha_compress", sha_compress, MT.sha_compress_shard_from),
-                             ("uint256", uint256, MT.uint256_shard_from), ("secp256k1_add", secp_add, MT.secp256k1_add_shard_from),
-                             ("secp256k1_double", secp_double, MT.secp256k1_double_shard_from)):
-        for part in chunks(name, evs):
-            if name in untraced_precompile:
-                assert name in DEVICE_PRECOMPILE_KINDS, name
-                yield name, None, None, ctx, None, part
-                continue
-            machine, tables, publics, gev = build(part, device, ctx=ctx)
-            if secp_events is not None and name.startswith("secp256k1_"):
-                secp_events.append((name, part))
-            yield name, machine, tables, publics, gev, None
-    for kind in FAMILIES:                                    # one chip per kind; Fp / UINT256 kinds hold all their system calls' events
-        for part in chunks(kind, families.get(kind)):
-            machine, tables, publics, gev = MT.family_shard_from(kind, part, device, ctx=ctx)
-            yield kind, machine, tables, publics, gev, None
+    for kind in PRECOMPILE_KINDS + tuple(FAMILIES):          # one chip per family kind; Fp / UINT256 kinds hold all their system calls' events
+        if kind in calls:
+            events = np.concatenate(calls[kind])
+            for at in range(0, events.shape[0], limit[kind]):
+                yield ShardRecords(kind, ctx, events=events[at:at + limit[kind]])
     # ---- the memory shards (prover/src/worker/controller/global.rs:L145-L300). Every touched address — registers with a timestamp,
     # memory words, hinted words — is finalised, and so is every word of the program's memory image, touched or not; every touched
     # address OUTSIDE the image is initialised (registers and fresh memory with 0, hinted words with their hint). The image's own
@@ -889,16 +853,46 @@ def program_shards(executor, max_cycles, device="cpu", core_limit=None, keccak_e
     for at in range(0, fin_addr.shape[0], limit["memory"]):
         fa, fr = fin_addr[at:at + limit["memory"]], fin_rec[at:at + limit["memory"]]
         lo, hi = np.searchsorted(init_addr, fa[0], side="left"), np.searchsorted(init_addr, fa[-1], side="right")
-        if untraced_memory:
-            yield "memory", None, None, ctx, None, (init_addr[lo:hi], init_rec[lo:hi], fa, fr, previous_init, previous_fin)
-            previous_init = int(init_addr[hi - 1]) if hi > lo else previous_init
-            previous_fin = int(fa[-1])
-            continue
-        machine, tables, publics, gev = MT.memory_shard_from(init_addr[lo:hi], init_rec[lo:hi], fr, device, previous_addr=previous_init, ctx=ctx,
-                                                             fin_addrs=fa, previous_fin_addr=previous_fin)
+        yield ShardRecords("memory", ctx, init_addrs=init_addr[lo:hi], init_recs=init_rec[lo:hi], fin_addrs=fa, fin_recs=fr,
+                           previous_init=previous_init, previous_fin=previous_fin)
         previous_init = int(init_addr[hi - 1]) if hi > lo else previous_init
         previous_fin = int(fa[-1])
-        yield "memory", machine, tables, publics, gev, None
+
+
+def host_shard(executor, rec, device="cpu"):
+    """(machine, tables, publics, global events [m, 11]) of one ShardRecords by the host tracer, tables = {name: (prep, main)}
+    canonical int64 tensors on `device`: a core shard through EventTracer, every other kind through the builder of its kind in
+    riscv_more_trace."""
+    from . import riscv_more_trace as MT
+    if rec.kind == "core":
+        tr = EventTracer(executor, rec.executed, device, prev=rec.prev)
+        return (*tr.build(), tr.global_events)
+    if rec.kind == "memory":
+        return MT.memory_shard_from(rec.init_addrs, rec.init_recs, rec.fin_recs, device, previous_addr=rec.previous_init, ctx=rec.ctx,
+                                    fin_addrs=rec.fin_addrs, previous_fin_addr=rec.previous_fin)
+
+    def keccak(events, device, ctx):                         # clk, pointer, 25 x (previous timestamp, word read), 25 words written
+        kk = torch.as_tensor(events, device=device)
+        rd = kk[:, 2:52].reshape(-1, 25, 2)
+        return MT.precompile_shard_from(kk[:, 0], kk[:, 1], rd[:, :, 1].contiguous(), rd[:, :, 0].contiguous(), device, ctx=ctx)
+
+    def poseidon2(events, device, ctx):                      # clk, pointer, 8 x (previous timestamp, word read), 8 words written
+        pp = torch.as_tensor(events, device=device)
+        rd = pp[:, 2:18].reshape(-1, 8, 2)
+        return MT.poseidon2_shard_from(pp[:, 0], pp[:, 1], rd[:, :, 1].contiguous(), rd[:, :, 0].contiguous(), pp[:, 18:26].contiguous(), device, ctx=ctx)
+    builders = {"keccak": keccak, "poseidon2": poseidon2, "sha_extend": MT.sha_extend_shard_from, "sha_compress": MT.sha_compress_shard_from,
+                "uint256": MT.uint256_shard_from, "secp256k1_add": MT.secp256k1_add_shard_from, "secp256k1_double": MT.secp256k1_double_shard_from,
+                **{kind: functools.partial(MT.family_shard_from, kind) for kind in FAMILIES}}
+    return builders[rec.kind](rec.events, device, ctx=rec.ctx)
+
+
+def program_shards(executor, max_cycles, device="cpu", core_limit=None):
+    """Every shard of a run traced on the host, in run_records' order: `(kind, machine, tables, publics, global events, ExecutedShard
+    or None)` — host_shard of each record; the last slot holds a core shard's ExecutedShard. The global events of all shards cancel
+    as a multiset: that is the statement the shards' septic-curve digests add up to. A caller that wants the records themselves, or
+    shards made on the device (device_shard), iterates run_records."""
+    for rec in run_records(executor, max_cycles, core_limit):
+        yield (rec.kind, *host_shard(executor, rec, device), rec.executed)
 
 
 def image_events(executor, device="cpu"):

@@ -8,7 +8,7 @@ unshifted and shifted across 2^24 cycles (rv64_partition_cases).
 * EventTracer.__init__ is patched to raise while device_core_shard runs: the tracer is never built;
 * one shifted and one unshifted shard proved (L = 17): the bytes equal the oracle's proof from the same tables downloaded, for the
   unshifted shard also the proof from the host tracer's tables, and the pinned verifier accepts both with PVM.verifier_program();
-* program_shards(untraced_core=True) yields the shard with the previous public values and builds no tracer.
+* run_records yields the shard with the previous public values, and device_shard makes it, without a tracer being built.
 Everything is bit-exact; there are no tolerances."""
 import functools
 import os
@@ -149,17 +149,17 @@ def test_program_shards_yields_core_shards_untraced(api, monkeypatch):
     ex = X.Executor(A.elf(p.words + A.halt(0), data=K.data_bytes(), data_addr=K.DATA), stdin=[])
 
     def refuse(self, *a, **k):
-        raise AssertionError("program_shards built an EventTracer")
+        raise AssertionError("run_records or device_shard built an EventTracer")
     seen = []
     with monkeypatch.context() as mp:
         mp.setattr(X.EventTracer, "__init__", refuse)
-        gen = X.program_shards(ex, 1 << 20, device="cuda", untraced_core=True)
-        for kind, machine, tabs, prev, gev, sh in gen:
-            if kind != "core":
+        gen = X.run_records(ex, 1 << 20)
+        for rec in gen:
+            if rec.kind != "core":
                 break
-            assert machine is None and tabs is None and gev is None and prev is None and sh is not None
-            seen.append(X.device_core_shard(ex, sh, prep_of("core"), prev=prev))
-            if sh.halted:                                      # the precompile and memory shards behind it are not this test's
+            assert rec.prev is None and rec.events is None and rec.executed is not None
+            seen.append(X.device_shard(ex, rec, prep_of("core")))
+            if rec.executed.halted:                            # the precompile and memory shards behind it are not this test's
                 break
         gen.close()
     assert len(seen) == 1

@@ -205,12 +205,11 @@ def test_the_keccak_shard_of_a_real_guest(api):
     executor here, not from the filler), and a shard proof made with them is the proof from the host tables, byte for byte."""
     import core_real
     ex = X.Executor(X.guest_file("keccak.elf"), stdin=[bytes(300)])
-    kev = []
-    for kind, machine, tabs, publics, gev, sh in X.program_shards(ex, 6000, device="cuda", core_limit=0, keccak_events=kev):
-        if kind == "keccak":
-            break
-    else:
+    kev = [rec for rec in X.run_records(ex, 6000, core_limit=0) if rec.kind == "keccak"]
+    if not kev:
         pytest.fail("the guest made no Keccak shard")
+    machine, tabs, publics, gev = X.host_shard(ex, kev[0], "cuda")
+    kev = [rec.events for rec in kev]
     assert len(kev) == 1 and kev[0].shape[0] > 0 and kev[0].shape[1] == 77
     made = dict(zip(NAMES, MT.keccak_device_tables(kev[0], [tabs[name][1].shape[0] for name in NAMES])))
     dev = [(a, i, core_real.to_col_major(tabs[a.name][1]), core_real.to_col_major(tabs[a.name][0]) if tabs[a.name][0] is not None else None)

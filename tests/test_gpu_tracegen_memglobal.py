@@ -10,8 +10,8 @@
   list: every table and the public values are equal, and the proof is the same bytes as from the host-made tables and as the oracle's.
 * riscv_exec.device_precompile_shard against the host shard at the same counts; proof bytes equal for the 2-call Keccak shard and
   for both secp256k1 shards of the hand-assembled 2G / G + 2G / 6G program.
-* one run of program_shards with every flag on over a small fibonacci input: the Global events of all shards plus the image's
-  cancel, and PVM.verify_proof_public_values accepts the chain."""
+* one run of run_records over a small fibonacci input with every shard made by device_shard: the Global events of all shards plus
+  the image's cancel, and PVM.verify_proof_public_values accepts the chain."""
 import os
 import struct
 import sys
@@ -192,17 +192,17 @@ def test_device_precompile_shard_equals_the_host_shard(api, kind, n):
 
 def test_both_secp256k1_shards_of_a_program_prove_to_the_same_bytes(api):
     """2G, G + 2G, 6G by the precompiles from the hand-assembled program of test_gpu_tracegen_secp.py: the two shards made on the
-    device from the untraced events equal the traced ones and prove to the same bytes."""
+    device from the run's records equal the traced ones and prove to the same bytes."""
     import test_tracegen_memglobal_abi as T
     traced = {s[0]: s for s in X.program_shards(T._guest(), 1 << 20) if s[0].startswith("secp256k1_")}
-    seen = []
-    for kind, machine, tables, ctx, gev, events in X.program_shards(T._guest(), 1 << 20, untraced_precompile=set(X.DEVICE_PRECOMPILE_KINDS)):
+    ex, seen = T._guest(), []
+    for rec in X.run_records(ex, 1 << 20):
+        kind = rec.kind
         if not kind.startswith("secp256k1_"):
             continue
-        assert machine is None and tables is None and gev is None
         _, machine, tables, publics, gev, _ = traced[kind]
         chips = _host_chips(machine, tables)
-        device = X.device_precompile_shard(kind, events, _prep_of(chips), ctx)
+        device = X.device_shard(ex, rec, _prep_of(chips))
         _assert_same_shard((machine, chips, publics, gev), device, int(gev.shape[0]))
         assert _prove(api, device[1], device[2]) == _prove(api, chips, publics)
         seen.append(kind)
@@ -210,7 +210,7 @@ def test_both_secp256k1_shards_of_a_program_prove_to_the_same_bytes(api):
 
 
 def test_a_whole_run_with_every_shard_made_on_the_device(api, monkeypatch):
-    """fibonacci(20) with every flag of program_shards on: no shard has a host table and no tracer is built (the host tracer's
+    """fibonacci(20) with device_shard over every record of run_records: no shard has a host table and no tracer is built (the host tracer's
     entry points are patched to raise); the Global events of all shards and the image's initialisation cancel, and the public values
     chain from the entry point to HALT."""
     import core_real
@@ -224,18 +224,14 @@ def test_a_whole_run_with_every_shard_made_on_the_device(api, monkeypatch):
         monkeypatch.setattr(MT, name, no_tracer)
     ex = X.Executor(X.guest_file("fibonacci.elf"), stdin=[struct.pack("<Q", 20)])
     prep, kinds, pvs, gevs, entry = None, [], [], [], None
-    for kind, machine, tables, slot, gev, raw in X.program_shards(ex, 1 << 20, untraced_core=True, untraced_memory=True,
-                                                                  untraced_precompile=set(X.DEVICE_PRECOMPILE_KINDS)):
-        assert machine is None and tables is None and gev is None, kind
+    for rec in X.run_records(ex, 1 << 20):
+        kind = rec.kind
+        assert kind in X.DEVICE_KINDS, kind
         if prep is None:
             prep = {n: core_real.to_col_major(t) for n, t in X.preprocessed_tables(ex, "cuda").items()}
         if kind == "core":
-            entry = raw.pc_start if entry is None else entry
-            machine, chips, publics, gev9 = X.device_core_shard(ex, raw, prep, prev=slot)
-        elif kind == "memory":
-            machine, chips, publics, gev9 = X.device_memory_shard(*raw[:4], prep, slot, previous_init=raw[4], previous_fin=raw[5])
-        else:
-            machine, chips, publics, gev9 = X.device_precompile_shard(kind, raw, prep, slot)
+            entry = rec.executed.pc_start if entry is None else entry
+        machine, chips, publics, gev9 = X.device_shard(ex, rec, prep)
         assert frozenset(a.name for a, _ in machine) in RT.chip_clusters() and [c[0].name for c in chips] == [a.name for a, _ in machine]
         kinds.append(kind)
         pvs.append([int(v) for v in publics])

@@ -134,15 +134,16 @@ def test_both_shards_of_a_program_with_the_system_calls(api):
     prog += [A.enc("addi", 10, 28, 64), A.enc("addi", 11, 28, 0)] + A.li(5, 0x0001010A) + [A.enc("ecall")]        # q = G + 2G
     prog += [A.enc("addi", 10, 28, 64), A.enc("addi", 11, 0, 0)] + A.li(5, 0x0000010B) + [A.enc("ecall")]         # q = 6G
     ex = X.Executor(A.elf(prog + A.halt(0), data=data + bytes(32)), stdin=[])
-    sev, seen = [], []
+    seen = []
     L, lsh, batch = 17, 12, 8
-    for kind, machine, tabs, publics, gev, sh in X.program_shards(ex, 1 << 20, secp_events=sev):
+    for rec in X.run_records(ex, 1 << 20):
+        kind, events = rec.kind, rec.events
         if not kind.startswith("secp256k1_"):
             continue
+        machine, tabs, publics, gev = X.host_shard(ex, rec)
         short = kind[len("secp256k1_"):]
         chip = SC.CHIPS[short]
-        name, events = sev.pop()
-        assert name == kind and events.shape == ({"add": 1, "double": 2}[short], SC.WORDS[short])
+        assert events.shape == ({"add": 1, "double": 2}[short], SC.WORDS[short])
         host = tabs[chip][1]
         made = MT.secp256k1_device_table(short, events, int(host.shape[0]))
         want = core_real.to_col_major(host.cuda())

@@ -578,13 +578,21 @@ def tracegen_riscv_mem(chip, events, height, stream=None):
     return _tracegen_records("sp1hip_tracegen_riscv_mem", MEM_EVENT_WORDS, RISCV_MEM_CHIPS[chip], events, height, stream)
 
 
+def _n_records(records, words=None):
+    """How many records a tracegen wrapper was handed, having checked them: an int64 tensor [n, words] (any width when `words` is
+    None), on the device and contiguous unless it is empty."""
+    n = int(records.shape[0])
+    assert records.dtype == torch.int64 and (words is not None or records.dim() == 2)
+    assert n == 0 or (records.is_cuda and records.is_contiguous() and (words is None or records.shape[1] == words))
+    return n
+
+
 def _tracegen_records(fn, words, kind, events, height, stream):
     """The body of every wrapper whose entry point makes one table from one stream of fixed-size records: `fn` the entry point
     (its width query is fn + "_width"), `words` the record's u64 words, `kind` the leading chip argument of both or None."""
     lead = () if kind is None else (kind,)
     width = getattr(_L(), fn + "_width")(*lead)
-    n = int(events.shape[0])
-    assert events.dtype == torch.int64 and (n == 0 or (events.is_cuda and events.shape[1] == words and events.is_contiguous()))
+    n = _n_records(events, words)
     out = device_words(width * int(height))
     check(getattr(_L(), fn)(*lead, _dptr(out), int(height), _dptr(events) if n else None, n, _stream_ptr(stream)))
     return ColMajor(out, int(height), width)
@@ -606,19 +614,33 @@ def tracegen_riscv_alu_x0(events, height, stream=None):
 MEMORY_LOCAL_RECORD_WORDS, MEMORY_LOCAL_WIDTH, GLOBAL_EVENT_WORDS = 5, 20, 9
 
 
+def _new_global_events(rows, extra, device, stream):
+    """The tensor [rows + extra, 9] a chip's Global events go to: the kernel writes every word of the first `rows` rows, the `extra`
+    rows behind them are the caller's to fill and are zero."""
+    events = torch.empty((rows + extra, GLOBAL_EVENT_WORDS), dtype=torch.int32, device=device)
+    if extra:
+        with torch.cuda.stream(stream or torch.cuda.current_stream()):
+            events[rows:].zero_()
+    return events
+
+
+def _global_events_ptr(global_events, n):
+    """A `global_events` argument checked — None, or an int32 device tensor [n, 9] — as the pointer the entry point takes."""
+    if global_events is None:
+        return None
+    assert global_events.dtype == torch.int32 and tuple(global_events.shape) == (n, GLOBAL_EVENT_WORDS) and global_events.is_contiguous()
+    return _dptr(global_events) if n else None
+
+
 def tracegen_riscv_memory_local(records, height, extra_global_events=0, stream=None):
     """`generate_trace_device` for the MemoryLocal chip (sp1hip_tracegen_riscv_memory_local): records = a device int64 tensor [n, 5]
     of the executor's local-memory records (riscv_exec.ExecutedShard.local: addr, initial clk, initial value, final clk, final
     value). Returns (the column-major [20][height] table as a ColMajor, the rows' Global events: an int32 device tensor
     [2 n + extra_global_events, 9] in the form tracegen_riscv_global reads, record i at rows 2 i and 2 i + 1; the
     `extra_global_events` rows behind them are the caller's to fill — SyscallCore's events — and are zero)."""
-    n, extra = int(records.shape[0]), int(extra_global_events)
-    assert records.dtype == torch.int64 and (n == 0 or (records.is_cuda and records.shape[1] == MEMORY_LOCAL_RECORD_WORDS and records.is_contiguous()))
+    n = _n_records(records, MEMORY_LOCAL_RECORD_WORDS)
     out = device_words(MEMORY_LOCAL_WIDTH * int(height))
-    events = torch.empty((2 * n + extra, GLOBAL_EVENT_WORDS), dtype=torch.int32, device=out.device)
-    if extra:                                                 # the kernel writes every word of the first 2 n rows
-        with torch.cuda.stream(stream or torch.cuda.current_stream()):
-            events[2 * n:].zero_()
+    events = _new_global_events(2 * n, int(extra_global_events), out.device, stream)
     check(_L().sp1hip_tracegen_riscv_memory_local(_dptr(out), int(height), _dptr(records) if n else None, n, _dptr(events) if n else None,
                                                   _stream_ptr(stream)))
     return ColMajor(out, int(height), MEMORY_LOCAL_WIDTH), events
@@ -636,13 +658,9 @@ def tracegen_riscv_memory_global(kind, records, height, previous_addr, extra_glo
     rows' Global events: an int32 device tensor [n + extra_global_events, 9] in the form tracegen_riscv_global reads, record i at
     row i — Init sends at timestamp zero, Finalize receives at the record's; the `extra_global_events` rows behind them are the
     caller's to fill and are zero)."""
-    n, extra = int(records.shape[0]), int(extra_global_events)
-    assert records.dtype == torch.int64 and (n == 0 or (records.is_cuda and records.shape[1] == MEMORY_GLOBAL_RECORD_WORDS and records.is_contiguous()))
+    n = _n_records(records, MEMORY_GLOBAL_RECORD_WORDS)
     out = device_words(MEMORY_GLOBAL_WIDTH * int(height))
-    events = torch.empty((n + extra, GLOBAL_EVENT_WORDS), dtype=torch.int32, device=out.device)
-    if extra:                                                 # the kernel writes every word of the first n rows
-        with torch.cuda.stream(stream or torch.cuda.current_stream()):
-            events[n:].zero_()
+    events = _new_global_events(n, int(extra_global_events), out.device, stream)
     check(_L().sp1hip_tracegen_riscv_memory_global(MEMORY_GLOBAL_KINDS[kind], _dptr(out), int(height), _dptr(records) if n else None, n,
                                                    int(previous_addr) & ((1 << 64) - 1), _dptr(events) if n else None, _stream_ptr(stream)))
     return ColMajor(out, int(height), MEMORY_GLOBAL_WIDTH), events
@@ -663,14 +681,11 @@ def tracegen_riscv_syscall_precompile(events, height, syscall_id, arg2_word=-1, 
     `arg2_word` the second or -1). Returns the column-major [10][height] table as a ColMajor, one row per call. `global_events`: an
     int32 device tensor [n, 9] that receives the rows' Global events — receives of kind Syscall — in the form tracegen_riscv_global
     reads: the tail tracegen_riscv_memory_local leaves for them; or None."""
-    n = int(events.shape[0])
-    assert events.dtype == torch.int64 and events.dim() == 2 and (n == 0 or (events.is_cuda and events.is_contiguous()))
-    if global_events is not None:
-        assert global_events.dtype == torch.int32 and tuple(global_events.shape) == (n, GLOBAL_EVENT_WORDS) and global_events.is_contiguous()
+    n = _n_records(events)
+    d_global_events = _global_events_ptr(global_events, n)
     out = device_words(SYSCALL_PRECOMPILE_WIDTH * int(height))
     check(_L().sp1hip_tracegen_riscv_syscall_precompile(_dptr(out), int(height), _dptr(events) if n else None, n, int(events.shape[1]), int(syscall_id),
-                                                        int(arg2_word), _dptr(global_events) if n and global_events is not None else None,
-                                                        _stream_ptr(stream)))
+                                                        int(arg2_word), d_global_events, _stream_ptr(stream)))
     return ColMajor(out, int(height), SYSCALL_PRECOMPILE_WIDTH)
 
 
@@ -736,13 +751,10 @@ def tracegen_riscv_syscall_core(events, height, global_events=None, stream=None)
     [n, 9] that receives the rows' Global events in the form tracegen_riscv_global reads — the tail tracegen_riscv_memory_local leaves
     for them — or None."""
     width = _L().sp1hip_tracegen_riscv_syscall_core_width()
-    n = int(events.shape[0])
-    assert events.dtype == torch.int64 and (n == 0 or (events.is_cuda and events.shape[1] == ALU_EVENT_WORDS and events.is_contiguous()))
-    if global_events is not None:
-        assert global_events.dtype == torch.int32 and tuple(global_events.shape) == (n, GLOBAL_EVENT_WORDS) and global_events.is_contiguous()
+    n = _n_records(events, ALU_EVENT_WORDS)
+    d_global_events = _global_events_ptr(global_events, n)
     out = device_words(width * int(height))
-    check(_L().sp1hip_tracegen_riscv_syscall_core(_dptr(out), int(height), _dptr(events) if n else None, n,
-                                                  _dptr(global_events) if n and global_events is not None else None, _stream_ptr(stream)))
+    check(_L().sp1hip_tracegen_riscv_syscall_core(_dptr(out), int(height), _dptr(events) if n else None, n, d_global_events, _stream_ptr(stream)))
     return ColMajor(out, int(height), width)
 
 

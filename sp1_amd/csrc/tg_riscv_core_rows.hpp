@@ -21,7 +21,7 @@ namespace tg {
 enum : uint32_t { OP_DIV = 15, OP_DIVU = 16, OP_REM = 17, OP_REMU = 18, OP_DIVW = 25, OP_DIVUW = 26, OP_REMW = 27, OP_REMUW = 28 };
 
 constexpr int DIVREM_WIDTH = 246, ALU_X0_WIDTH = 34, MEMORY_LOCAL_WIDTH = 20;
-constexpr int MEMORY_LOCAL_RECORD_WORDS = 5, GLOBAL_EVENT_WORDS = 9;
+constexpr int MEMORY_LOCAL_RECORD_WORDS = 5;
 constexpr uint32_t KIND_MEMORY = 1;                           // InteractionKind::Memory
 
 namespace col {
@@ -263,6 +263,44 @@ TG_HD void memory_local_global_events(int32_t* out, const uint64_t* rec) {
         o[8] = (int32_t)((k == 0 ? 1u : 0u) | KIND_MEMORY << 8);
     }
 }
+
+// One lane's (one host iteration's) whole DivRem row: each column group from its zeros, stored before the next is made. The chip
+// keeps this body of its own instead of row_kernel's because a whole 246-word row would go to scratch (above)
+template <int PART> TG_HD void divrem_store_part(uint32_t* __restrict__ out, uint32_t height, uint32_t row, bool live, const Ev& e, const DivRemVals& d) {
+    constexpr int LO = divrem_part_at(PART), HI = divrem_part_at(PART + 1);
+    Row<DIVREM_WIDTH> r;
+    zero_cols<LO, HI>(r);
+    if (live) fill_divrem<PART>(r, e, d); else fill_divrem_padding<PART>(r);
+    store_cols<LO, HI>(out, height, row, r);
+}
+TG_HD void divrem_row(uint32_t* __restrict__ out, uint32_t height, const Ev* __restrict__ events, uint32_t n, uint32_t row) {
+    const bool live = row < n;
+    Ev e = {};
+    if (live) e = events[row];
+    const DivRemVals d = divrem_values(e);
+    divrem_store_part<0>(out, height, row, live, e, d);
+    divrem_store_part<1>(out, height, row, live, e, d);
+    divrem_store_part<2>(out, height, row, live, e, d);
+    divrem_store_part<3>(out, height, row, live, e, d);
+}
+
+// The chips of row_kernel / host_rows (tg_row_kernel.hpp)
+struct AluX0 : ZeroPaddedChip<ALU_X0_WIDTH, Ev> {
+    static TG_HD void live(Row<WIDTH>& r, const Ev* __restrict__ events, uint32_t row) { fill_alu_x0(r, events[row]); }
+};
+// `global_events` (may be null): [2 n][9] words, record i's receive at row 2 i and its send at row 2 i + 1
+struct MemoryLocal : ZeroPaddedChip<MEMORY_LOCAL_WIDTH, uint64_t> {
+    static TG_HD void live(Row<WIDTH>& r, const uint64_t* __restrict__ records, uint32_t row, int32_t* __restrict__ global_events) {
+        uint64_t rec[MEMORY_LOCAL_RECORD_WORDS];
+        load_record<MEMORY_LOCAL_RECORD_WORDS>(rec, records, row);
+        fill_memory_local(r, rec);
+        if (global_events) {
+            int32_t ev[2 * GLOBAL_EVENT_WORDS];
+            memory_local_global_events(ev, rec);
+            store_global_events<2>(global_events, row, ev);
+        }
+    }
+};
 
 }  // namespace tg
 }  // namespace sp1hip

@@ -128,5 +128,10 @@ template <int CHIP> TG_HD void fill_mem_row(Row<mem_width_of(CHIP)>& r, const Me
 // events with write_bytes(.., 0, ..) (load_byte.rs:L135-L141 and the same lines of the eight others), and the host tracer's
 // tables start as zeros (riscv_trace.Table); the tests compare the padding rows word for word
 
+// The chip of row_kernel / host_rows (tg_row_kernel.hpp) for each of the nine
+template <int CHIP> struct LoadStoreChip : ZeroPaddedChip<mem_width_of(CHIP), MemEv> {
+    static TG_HD void live(Row<mem_width_of(CHIP)>& r, const MemEv* __restrict__ events, uint32_t row) { fill_mem_row<CHIP>(r, events[row]); }
+};
+
 }  // namespace tg
 }  // namespace sp1hip

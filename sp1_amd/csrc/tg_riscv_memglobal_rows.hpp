@@ -93,6 +93,37 @@ TG_HD void syscall_precompile_global_event(int32_t* o, const uint64_t* ev, uint3
     o[8] = (int32_t)(1u | KIND_SYSCALL << 8);
 }
 
+// The chips of row_kernel / host_rows (tg_row_kernel.hpp). `global_events` (may be null): [n][9] words, row i's event at row i.
+// MemoryGlobal's row i reads record i and the ADDRESS of record i - 1 (the call's previous_addr for row 0): the one neighbour read
+// among the chips. On the device it is a second load of a word the lane before loads as its own, not an exchange between lanes, so
+// it is the same at a wave's and a workgroup's first lane as anywhere else.
+struct MemoryGlobal : ZeroPaddedChip<MEMORY_GLOBAL_WIDTH, uint64_t> {
+    static TG_HD void live(Row<WIDTH>& r, const uint64_t* __restrict__ records, uint32_t row, uint64_t previous_addr, int finalize,
+                           int32_t* __restrict__ global_events) {
+        uint64_t rec[MEMORY_GLOBAL_RECORD_WORDS];
+        load_record<MEMORY_GLOBAL_RECORD_WORDS>(rec, records, row);
+        const uint64_t prev = row ? records[(size_t)(row - 1) * MEMORY_GLOBAL_RECORD_WORDS] : previous_addr;
+        fill_memory_global(r, rec, prev, row);
+        if (global_events) {
+            int32_t ev[GLOBAL_EVENT_WORDS];
+            memory_global_event(ev, rec, finalize != 0);
+            store_global_events<1>(global_events, row, ev);
+        }
+    }
+};
+struct SyscallPrecompile : ZeroPaddedChip<SYSCALL_PRECOMPILE_WIDTH, uint64_t> {
+    static TG_HD void live(Row<WIDTH>& r, const uint64_t* __restrict__ events, uint32_t row, uint32_t words_per_event, uint32_t syscall_id, int arg2_word,
+                           int32_t* __restrict__ global_events) {
+        const uint64_t* e = events + (size_t)row * words_per_event;
+        fill_syscall_precompile(r, e, syscall_id, arg2_word);
+        if (global_events) {
+            int32_t ev[GLOBAL_EVENT_WORDS];
+            syscall_precompile_global_event(ev, e, syscall_id, arg2_word);
+            store_global_events<1>(global_events, row, ev);
+        }
+    }
+};
+
 // One run of consecutive words a precompile touches through one pointer: event word ptr_word holds the pointer, `count` words
 // follow it in memory; event words pairs_word + 2 i, + 2 i + 1 hold word i's previous timestamp and value, event word final_word + i
 // the value the call leaves (PRECOMPILE_NO_WORD: the words are only read and keep theirs); the call's last access to them is at

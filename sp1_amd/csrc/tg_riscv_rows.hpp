@@ -1,5 +1,5 @@
 // sp1_amd/csrc/tg_riscv_rows.hpp — the rows of the RISC-V instruction chips whose tables tracegen_riscv.hip makes on the device,
-// for host and device code alike (as tg_field_op.hpp is for the precompile chips): the event record, a row held as W words, the
+// for host and device code alike (as tg_field_op.hpp is for the precompile chips): the event record (a row held as W words is tg_row_kernel.hpp's Row), the
 // column groups the chips share (CPUState, the register access columns, the R / I / ALU / J adapters, the signed / unsigned
 // compare) and fill_row<CHIP> for each of the fourteen chips. tests/native/riscv_rows.hip runs the same functions on the CPU, so
 // every word can be compared with the host tracer (sp1_amd/machines/riscv_trace.py, riscv_exec.py) without a GPU.
@@ -23,16 +23,11 @@
 // are what the tests compare the constants below with). Every index into Row::c and every limb index is a constant (fully
 // unrolled loops), so on the device a row is registers.
 #pragma once
-#include "kb31.hpp"
-
-#ifndef TG_HD
-#define TG_HD __host__ __device__ __forceinline__
-#endif
+#include "tg_row_kernel.hpp"
 
 namespace sp1hip {
 namespace tg {
 
-constexpr uint32_t M16 = 0xffffu;
 // flags of sp1hip_rv64_alu_event_t.ops (bits 32..): operand b / c is an immediate
 constexpr uint64_t F_IMM_C = 1ull << 33;                     // (bit 32: operand b is an immediate — JAL, LUI, AUIPC; it travels as b)
 constexpr uint32_t POS_C = 2, POS_B = 3, POS_A = 4;         // MemoryAccessPosition (core/executor/src/events/memory.rs:L63-L74)
@@ -43,12 +38,6 @@ struct Ev { uint64_t pc, clk, ops, a, b, c, a_prev, a_pts, b_pts, c_pts, aux; };
 enum : uint32_t { OP_SRL = 7, OP_SRA = 8, OP_MUL = 11, OP_MULH = 12, OP_MULHU = 13, OP_MULHSU = 14, OP_SRLW = 22, OP_SRAW = 23, OP_MULW = 24,
                   OP_BEQ = 40, OP_BNE = 41, OP_BLT = 42, OP_BGE = 43, OP_BLTU = 44, OP_BGEU = 45 };
 enum : uint32_t { OP_XOR = 3, OP_OR = 4, OP_AND = 5, OP_SLL = 6, OP_SLT = 9, OP_SLTU = 10, OP_SLLW = 21, OP_AUIPC = 48 };
-
-template <int W> struct Row {
-    uint32_t c[W];
-    TG_HD void limbs4(int at, uint64_t v) { c[at] = v & M16; c[at + 1] = (v >> 16) & M16; c[at + 2] = (v >> 32) & M16; c[at + 3] = (v >> 48) & M16; }
-    TG_HD void limbs3(int at, uint64_t v) { c[at] = v & M16; c[at + 1] = (v >> 16) & M16; c[at + 2] = (v >> 32) & M16; }
-};
 
 // CPUState at columns 0..5
 template <int W> TG_HD void fill_state(Row<W>& r, const Ev& e) {
@@ -301,6 +290,14 @@ template <int CHIP> TG_HD void fill_padding(Row<width_of(CHIP)>& r) {
     if (CHIP == SHIFT_RIGHT) { r.c[47] = 16; r.c[46] = 256; r.c[45] = 65536; }       // the padded row template (alu/sr/mod.rs:L165-L171)
     if (CHIP == SHIFT_LEFT) { r.c[col::SLL_V_01] = 1; r.c[col::SLL_V_012] = 1; r.c[col::SLL_V_0123] = 1; }   // alu/sll/mod.rs:L154-L160
 }
+
+// The chip of row_kernel / host_rows (tg_row_kernel.hpp) for each of the fourteen
+template <int CHIP> struct AluChip {
+    static constexpr int WIDTH = width_of(CHIP);
+    using Rec = Ev;
+    static TG_HD void live(Row<WIDTH>& r, const Ev* __restrict__ events, uint32_t row) { fill_row<CHIP>(r, events[row]); }
+    static TG_HD void padding(Row<WIDTH>& r) { fill_padding<CHIP>(r); }
+};
 
 }  // namespace tg
 }  // namespace sp1hip

@@ -123,5 +123,36 @@ TG_HD void fill_memory_bump(Row<MEMORY_BUMP_WIDTH>& r, const uint64_t* rec) {
     r.c[c::MB_IS_REAL] = 1;
 }
 
+// The chips of row_kernel / host_rows (tg_row_kernel.hpp)
+struct SyscallInstrs : ZeroPaddedChip<SYSCALL_INSTRS_WIDTH, Ev> {
+    static TG_HD void live(Row<WIDTH>& r, const Ev* __restrict__ events, uint32_t row) { fill_syscall_instrs(r, events[row]); }
+};
+// `global_events` (may be null): [n][9] words, row i's send at row i
+struct SyscallCore : ZeroPaddedChip<SYSCALL_CORE_WIDTH, Ev> {
+    static TG_HD void live(Row<WIDTH>& r, const Ev* __restrict__ events, uint32_t row, int32_t* __restrict__ global_events) {
+        const Ev e = events[row];
+        fill_syscall_core(r, e);
+        if (global_events) {
+            int32_t ev[GLOBAL_EVENT_WORDS];
+            syscall_core_global_event(ev, e);
+            store_global_events<1>(global_events, row, ev);
+        }
+    }
+};
+struct StateBump : ZeroPaddedChip<STATE_BUMP_WIDTH, uint64_t> {
+    static TG_HD void live(Row<WIDTH>& r, const uint64_t* __restrict__ records, uint32_t row) {
+        uint64_t rec[STATE_BUMP_RECORD_WORDS];
+        load_record<STATE_BUMP_RECORD_WORDS>(rec, records, row);
+        fill_state_bump(r, rec);
+    }
+};
+struct MemoryBump : ZeroPaddedChip<MEMORY_BUMP_WIDTH, uint64_t> {
+    static TG_HD void live(Row<WIDTH>& r, const uint64_t* __restrict__ records, uint32_t row) {
+        uint64_t rec[MEMORY_BUMP_RECORD_WORDS];
+        load_record<MEMORY_BUMP_RECORD_WORDS>(rec, records, row);
+        fill_memory_bump(r, rec);
+    }
+};
+
 }  // namespace tg
 }  // namespace sp1hip

@@ -21,6 +21,7 @@
 // of the zero state's permutation, so padding row q is its round q mod 24) with is_real = 0.
 #include "device_ctx.hpp"
 #include "tg_field_op.hpp"
+#include "tg_row_kernel.hpp"
 
 namespace sp1hip {
 namespace tgk {
@@ -159,20 +160,11 @@ int sp1hip_tracegen_riscv_keccak_control_width(void) { return tgk::CONTROL_WIDTH
 
 int sp1hip_tracegen_riscv_keccak(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream) {
     SP1HIP_REQUIRE((uint64_t)n_events * tgk::ROUNDS <= height, "the events' rows (24 each) exceed the height");
-    SP1HIP_REQUIRE((d_table || height == 0) && (d_events || n_events == 0), "null pointer");
-    if (height == 0) return SP1HIP_SUCCESS;
-    hipLaunchKernelGGL(tgk::keccak_permute_kernel, dim3((height + 255) / 256), dim3(256), 0, S(stream), d_table, height, d_events, n_events);
-    SP1HIP_LAUNCH_CHECK();
-    return SP1HIP_SUCCESS;
+    return tg::launch_rows(__func__, tgk::keccak_permute_kernel, d_table, height, d_events, n_events, stream);
 }
 
 int sp1hip_tracegen_riscv_keccak_control(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream) {
-    SP1HIP_REQUIRE(n_events <= height, "more events than rows");
-    SP1HIP_REQUIRE((d_table || height == 0) && (d_events || n_events == 0), "null pointer");
-    if (height == 0) return SP1HIP_SUCCESS;
-    hipLaunchKernelGGL(tgk::keccak_control_kernel, dim3((height + 255) / 256), dim3(256), 0, S(stream), d_table, height, d_events, n_events);
-    SP1HIP_LAUNCH_CHECK();
-    return SP1HIP_SUCCESS;
+    return tg::launch_rows(__func__, tgk::keccak_control_kernel, d_table, height, d_events, n_events, stream);
 }
 
 }  // extern "C"

@@ -10,35 +10,14 @@
 // operations each, so the kernels run at the rate the table can be written.
 //
 // The rows themselves — the event record, the column groups, fill_row<CHIP> with the reference's files and lines at each chip —
-// are tg_riscv_rows.hpp, host and device code alike (tests/native/riscv_rows.hip runs them on the CPU). This file is the kernel,
-// the launch switch and the ABI. Output: column-major [width][height] Montgomery words, rows >= n_events are the chip's padding
-// rows.
+// are tg_riscv_rows.hpp, host and device code alike (tests/native/riscv_rows.hip runs them on the CPU); the kernel and its launch
+// are tg_row_kernel.hpp. This file is the launch switch and the ABI. Output: column-major [width][height] Montgomery words, rows
+// >= n_events are the chip's padding rows.
 #include "device_ctx.hpp"
 #include "tg_riscv_rows.hpp"
 
-namespace sp1hip {
-namespace tg {
-
-static_assert(sizeof(Ev) == sizeof(sp1hip_rv64_alu_event_t), "event layout");
-
-template <int CHIP>
-__global__ __launch_bounds__(256) void tracegen_alu_kernel(uint32_t* __restrict__ out, uint32_t height, const Ev* __restrict__ events, uint32_t n) {
-    constexpr int W = width_of(CHIP);
-    const uint32_t row = blockIdx.x * 256u + threadIdx.x;
-    if (row >= height) return;
-    Row<W> r;
-#pragma unroll
-    for (int c = 0; c < W; c++) r.c[c] = 0;
-    if (row < n) fill_row<CHIP>(r, events[row]);
-    else fill_padding<CHIP>(r);
-#pragma unroll
-    for (int c = 0; c < W; c++) gptr(out)[(size_t)c * height + row] = r.c[c] ? kb::to_monty(r.c[c]) : 0u;
-}
-
-}  // namespace tg
-}  // namespace sp1hip
-
 using namespace sp1hip;
+static_assert(sizeof(tg::Ev) == sizeof(sp1hip_rv64_alu_event_t), "event layout");
 
 extern "C" {
 
@@ -47,19 +26,14 @@ int sp1hip_tracegen_riscv_alu_width(int chip) { return chip >= 0 && chip < tg::N
 int sp1hip_tracegen_riscv_alu(int chip, uint32_t* d_table, uint32_t height, const sp1hip_rv64_alu_event_t* d_events, uint32_t n_events,
                               sp1hip_stream_t stream) {
     SP1HIP_REQUIRE(chip >= 0 && chip < tg::N_CHIPS, "unknown chip");
-    SP1HIP_REQUIRE(n_events <= height && (d_table || height == 0) && (d_events || n_events == 0), "bad argument");
-    if (height == 0) return SP1HIP_SUCCESS;
-    hipStream_t s = S(stream);
-    const dim3 grid((height + 255) / 256), block(256);
     const tg::Ev* ev = reinterpret_cast<const tg::Ev*>(d_events);
     switch (chip) {
-#define SP1HIP_TG(C) case tg::C: hipLaunchKernelGGL(tg::tracegen_alu_kernel<tg::C>, grid, block, 0, s, d_table, height, ev, n_events); break
+#define SP1HIP_TG(C) case tg::C: return tg::launch_rows(__func__, tg::row_kernel<tg::AluChip<tg::C>>, d_table, height, ev, n_events, stream)
         SP1HIP_TG(ADD); SP1HIP_TG(ADDI); SP1HIP_TG(SUB); SP1HIP_TG(ADDW); SP1HIP_TG(SUBW); SP1HIP_TG(MUL); SP1HIP_TG(SHIFT_RIGHT); SP1HIP_TG(BRANCH);
         SP1HIP_TG(BITWISE); SP1HIP_TG(LT); SP1HIP_TG(SHIFT_LEFT); SP1HIP_TG(UTYPE); SP1HIP_TG(JAL); SP1HIP_TG(JALR);
 #undef SP1HIP_TG
     }
-    SP1HIP_LAUNCH_CHECK();
-    return SP1HIP_SUCCESS;
+    return SP1HIP_ERROR_INVALID_ARGUMENT;                    // not reached: every chip of the range has its case
 }
 
 }  // extern "C"

@@ -9,33 +9,13 @@
 // rate the table can be written.
 //
 // The rows themselves are tg_riscv_mem_rows.hpp, host and device code alike (tests/native/riscv_mem_rows.hip runs them on the
-// CPU). This file is the kernel, the launch switch and the ABI. Output: column-major [width][height] Montgomery words, rows >=
-// n_events are zero rows.
+// CPU); the kernel and its launch are tg_row_kernel.hpp. This file is the launch switch and the ABI. Output: column-major
+// [width][height] Montgomery words, rows >= n_events are zero rows.
 #include "device_ctx.hpp"
 #include "tg_riscv_mem_rows.hpp"
 
-namespace sp1hip {
-namespace tg {
-
-static_assert(sizeof(MemEv) == sizeof(sp1hip_rv64_mem_event_t), "event layout");
-
-template <int CHIP>
-__global__ __launch_bounds__(256) void tracegen_mem_kernel(uint32_t* __restrict__ out, uint32_t height, const MemEv* __restrict__ events, uint32_t n) {
-    constexpr int W = mem_width_of(CHIP);
-    const uint32_t row = blockIdx.x * 256u + threadIdx.x;
-    if (row >= height) return;
-    Row<W> r;
-#pragma unroll
-    for (int c = 0; c < W; c++) r.c[c] = 0;
-    if (row < n) fill_mem_row<CHIP>(r, events[row]);
-#pragma unroll
-    for (int c = 0; c < W; c++) gptr(out)[(size_t)c * height + row] = r.c[c] ? kb::to_monty(r.c[c]) : 0u;
-}
-
-}  // namespace tg
-}  // namespace sp1hip
-
 using namespace sp1hip;
+static_assert(sizeof(tg::MemEv) == sizeof(sp1hip_rv64_mem_event_t), "event layout");
 
 extern "C" {
 
@@ -44,19 +24,14 @@ int sp1hip_tracegen_riscv_mem_width(int chip) { return chip >= 0 && chip < tg::N
 int sp1hip_tracegen_riscv_mem(int chip, uint32_t* d_table, uint32_t height, const sp1hip_rv64_mem_event_t* d_events, uint32_t n_events,
                               sp1hip_stream_t stream) {
     SP1HIP_REQUIRE(chip >= 0 && chip < tg::N_MEM_CHIPS, "unknown chip");
-    SP1HIP_REQUIRE(n_events <= height && (d_table || height == 0) && (d_events || n_events == 0), "bad argument");
-    if (height == 0) return SP1HIP_SUCCESS;
-    hipStream_t s = S(stream);
-    const dim3 grid((height + 255) / 256), block(256);
     const tg::MemEv* ev = reinterpret_cast<const tg::MemEv*>(d_events);
     switch (chip) {
-#define SP1HIP_TG(C) case tg::C: hipLaunchKernelGGL(tg::tracegen_mem_kernel<tg::C>, grid, block, 0, s, d_table, height, ev, n_events); break
+#define SP1HIP_TG(C) case tg::C: return tg::launch_rows(__func__, tg::row_kernel<tg::LoadStoreChip<tg::C>>, d_table, height, ev, n_events, stream)
         SP1HIP_TG(LOAD_BYTE); SP1HIP_TG(LOAD_HALF); SP1HIP_TG(LOAD_WORD); SP1HIP_TG(LOAD_DOUBLE); SP1HIP_TG(LOAD_X0);
         SP1HIP_TG(STORE_BYTE); SP1HIP_TG(STORE_HALF); SP1HIP_TG(STORE_WORD); SP1HIP_TG(STORE_DOUBLE);
 #undef SP1HIP_TG
     }
-    SP1HIP_LAUNCH_CHECK();
-    return SP1HIP_SUCCESS;
+    return SP1HIP_ERROR_INVALID_ARGUMENT;                    // not reached: every chip of the range has its case
 }
 
 }  // extern "C"

@@ -6,66 +6,13 @@
 // The reference fills these tables on the host (`generate_trace_into` of crates/core/machine/src/memory/global.rs and
 // syscall/chip.rs; memory/local.rs for the records' rows) and copies them to the device. Here one lane fills one row. The rows
 // themselves are tg_riscv_memglobal_rows.hpp, host and device code alike (tests/native/riscv_memglobal_rows.hip runs them on the
-// CPU). This file is the kernels and the ABI. Output: column-major [width][height] Montgomery words, every column stored once, 64
-// consecutive words per wave.
-//
-// The MemoryGlobal lane of row i reads record i and the ADDRESS of record i - 1 (the call's previous_addr for row 0): the one
-// neighbour read among the row-per-lane kernels. It is a second load of a word the lane before loads as its own, not an exchange
-// between lanes, so it is the same at a wave's and a workgroup's first lane as anywhere else.
+// CPU); the kernel and its launch are tg_row_kernel.hpp. This file is the kernel of the MemoryLocal records and the ABI. Output:
+// column-major [width][height] Montgomery words, every column stored once, 64 consecutive words per wave.
 #include "device_ctx.hpp"
 #include "tg_riscv_memglobal_rows.hpp"
 
 namespace sp1hip {
 namespace tg {
-
-// `global_events` (may be null): [n][9] words, row i's event at row i
-__global__ __launch_bounds__(256) void tracegen_memory_global_kernel(uint32_t* __restrict__ out, uint32_t height, const uint64_t* __restrict__ records,
-                                                                     uint32_t n, uint64_t previous_addr, int finalize, int32_t* __restrict__ global_events) {
-    constexpr int W = MEMORY_GLOBAL_WIDTH;
-    const uint32_t row = blockIdx.x * 256u + threadIdx.x;
-    if (row >= height) return;
-    Row<W> r;
-#pragma unroll
-    for (int c = 0; c < W; c++) r.c[c] = 0;
-    if (row < n) {
-        uint64_t rec[MEMORY_GLOBAL_RECORD_WORDS];
-#pragma unroll
-        for (int i = 0; i < MEMORY_GLOBAL_RECORD_WORDS; i++) rec[i] = records[(size_t)row * MEMORY_GLOBAL_RECORD_WORDS + i];
-        const uint64_t prev = row ? records[(size_t)(row - 1) * MEMORY_GLOBAL_RECORD_WORDS] : previous_addr;
-        fill_memory_global(r, rec, prev, row);
-        if (global_events) {
-            int32_t ev[GLOBAL_EVENT_WORDS];
-            memory_global_event(ev, rec, finalize != 0);
-#pragma unroll
-            for (int i = 0; i < GLOBAL_EVENT_WORDS; i++) global_events[(size_t)row * GLOBAL_EVENT_WORDS + i] = ev[i];
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < W; c++) gptr(out)[(size_t)c * height + row] = r.c[c] ? kb::to_monty(r.c[c]) : 0u;
-}
-
-__global__ __launch_bounds__(256) void tracegen_syscall_precompile_kernel(uint32_t* __restrict__ out, uint32_t height, const uint64_t* __restrict__ events,
-                                                                          uint32_t n, uint32_t words_per_event, uint32_t syscall_id, int arg2_word,
-                                                                          int32_t* __restrict__ global_events) {
-    constexpr int W = SYSCALL_PRECOMPILE_WIDTH;
-    const uint32_t row = blockIdx.x * 256u + threadIdx.x;
-    if (row >= height) return;
-    Row<W> r;
-#pragma unroll
-    for (int c = 0; c < W; c++) r.c[c] = 0;
-    if (row < n) {
-        const uint64_t* e = events + (size_t)row * words_per_event;
-        fill_syscall_precompile(r, e, syscall_id, arg2_word);
-        if (global_events) {
-            int32_t ev[GLOBAL_EVENT_WORDS];
-            syscall_precompile_global_event(ev, e, syscall_id, arg2_word);
-#pragma unroll
-            for (int i = 0; i < GLOBAL_EVENT_WORDS; i++) global_events[(size_t)row * GLOBAL_EVENT_WORDS + i] = ev[i];
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < W; c++) gptr(out)[(size_t)c * height + row] = r.c[c] ? kb::to_monty(r.c[c]) : 0u;
-}
 
 // One lane per MemoryLocal record: [n_records][5] words
 __global__ __launch_bounds__(256) void precompile_local_records_kernel(uint64_t* __restrict__ records, uint32_t n_records, const uint64_t* __restrict__ events,
@@ -93,24 +40,17 @@ int sp1hip_tracegen_riscv_syscall_precompile_width(void) { return tg::SYSCALL_PR
 
 int sp1hip_tracegen_riscv_memory_global(int finalize, uint32_t* d_table, uint32_t height, const uint64_t* d_records, uint32_t n_records,
                                         uint64_t previous_addr, int32_t* d_global_events, sp1hip_stream_t stream) {
-    SP1HIP_REQUIRE((finalize == 0 || finalize == 1) && n_records <= height && (d_table || height == 0) && (d_records || n_records == 0), "bad argument");
-    if (height == 0) return SP1HIP_SUCCESS;
-    hipLaunchKernelGGL(tg::tracegen_memory_global_kernel, dim3((height + 255) / 256), dim3(256), 0, S(stream), d_table, height, d_records, n_records,
-                       previous_addr, finalize, d_global_events);
-    SP1HIP_LAUNCH_CHECK();
-    return SP1HIP_SUCCESS;
+    SP1HIP_REQUIRE(finalize == 0 || finalize == 1, "bad argument: finalize is 0 or 1");
+    return tg::launch_rows(__func__, tg::row_kernel<tg::MemoryGlobal, uint64_t, int, int32_t*>, d_table, height, d_records, n_records, stream, previous_addr,
+                           finalize, d_global_events);
 }
 
 int sp1hip_tracegen_riscv_syscall_precompile(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, uint32_t words_per_event,
                                              uint32_t syscall_id, int32_t arg2_word, int32_t* d_global_events, sp1hip_stream_t stream) {
-    SP1HIP_REQUIRE(n_events <= height && (d_table || height == 0) && (d_events || n_events == 0), "bad argument");
     SP1HIP_REQUIRE(words_per_event >= 2 && words_per_event <= 65536 && syscall_id < 256 && arg2_word >= -1 && arg2_word < (int32_t)words_per_event,
                    "bad event shape: need 2 <= words_per_event <= 65536, syscall_id < 256, -1 <= arg2_word < words_per_event");
-    if (height == 0) return SP1HIP_SUCCESS;
-    hipLaunchKernelGGL(tg::tracegen_syscall_precompile_kernel, dim3((height + 255) / 256), dim3(256), 0, S(stream), d_table, height, d_events, n_events,
-                       words_per_event, syscall_id, (int)arg2_word, d_global_events);
-    SP1HIP_LAUNCH_CHECK();
-    return SP1HIP_SUCCESS;
+    return tg::launch_rows(__func__, tg::row_kernel<tg::SyscallPrecompile, uint32_t, uint32_t, int, int32_t*>, d_table, height, d_events, n_events, stream,
+                           words_per_event, syscall_id, arg2_word, d_global_events);
 }
 
 int sp1hip_precompile_local_records(uint64_t* d_records, uint64_t records_capacity, const uint64_t* d_events, uint32_t n_events, uint32_t words_per_event,

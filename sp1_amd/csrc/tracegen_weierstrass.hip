@@ -16,6 +16,7 @@
 // dummy row, computed by the same code from p = (0, 0), q = (1, 1) (doubling: p = (0, 1)).
 #include "device_ctx.hpp"
 #include "tg_field_op.hpp"
+#include "tg_row_kernel.hpp"
 
 namespace sp1hip {
 namespace tgw {
@@ -58,23 +59,11 @@ int sp1hip_tracegen_riscv_secp256k1_add_width(void) { return tgw::Add::WIDTH; }
 int sp1hip_tracegen_riscv_secp256k1_double_width(void) { return tgw::Double::WIDTH; }
 
 int sp1hip_tracegen_riscv_secp256k1_add(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream) {
-    SP1HIP_REQUIRE(n_events <= height, "more events than rows");
-    SP1HIP_REQUIRE((d_table || height == 0) && (d_events || n_events == 0), "null pointer");
-    if (height == 0) return SP1HIP_SUCCESS;
-    hipLaunchKernelGGL(tgw::weierstrass_add_kernel, dim3((height + 255) / 256), dim3(256), 0, S(stream), d_table, height, d_events, n_events,
-                       tgw::secp256k1());
-    SP1HIP_LAUNCH_CHECK();
-    return SP1HIP_SUCCESS;
+    return tg::launch_rows(__func__, tgw::weierstrass_add_kernel, d_table, height, d_events, n_events, stream, tgw::secp256k1());
 }
 
 int sp1hip_tracegen_riscv_secp256k1_double(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream) {
-    SP1HIP_REQUIRE(n_events <= height, "more events than rows");
-    SP1HIP_REQUIRE((d_table || height == 0) && (d_events || n_events == 0), "null pointer");
-    if (height == 0) return SP1HIP_SUCCESS;
-    hipLaunchKernelGGL(tgw::weierstrass_double_kernel, dim3((height + 255) / 256), dim3(256), 0, S(stream), d_table, height, d_events, n_events,
-                       tgw::secp256k1(), fp256::small<tgw::N>(0));
-    SP1HIP_LAUNCH_CHECK();
-    return SP1HIP_SUCCESS;
+    return tg::launch_rows(__func__, tgw::weierstrass_double_kernel, d_table, height, d_events, n_events, stream, tgw::secp256k1(), fp256::small<tgw::N>(0));
 }
 
 }  // extern "C"

@@ -12,13 +12,9 @@
 //   riscv_core_rows host width                         "chip width" lines
 //
 // Build (done by __graft_entry__.build()): hipcc --offload-arch=gfx950 -O3 -std=c++17 -Isp1_amd/csrc -Iinclude ...
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
-#include <vector>
-
+#include "rows_io.hpp"
 #include "sp1hip.h"
 #include "tg_riscv_core_rows.hpp"
 
@@ -30,41 +26,12 @@ static const char* const NAMES[N_CORE_CHIPS] = {"DivRem", "AluX0", "MemoryLocal"
 static const int WIDTHS[N_CORE_CHIPS] = {tg::DIVREM_WIDTH, tg::ALU_X0_WIDTH, tg::MEMORY_LOCAL_WIDTH};
 static const size_t RECORD_WORDS[N_CORE_CHIPS] = {11, 11, tg::MEMORY_LOCAL_RECORD_WORDS};
 
-template <int W> static void put_row(uint32_t* out, uint32_t height, uint32_t row, const tg::Row<W>& r, int lo, int hi) {
-    for (int c = lo; c < hi; c++) out[(size_t)c * height + row] = r.c[c] ? kb::to_monty(r.c[c]) : 0u;
-}
-
-// what tracegen_divrem_kernel does for its lane: each column group from a zeroed row, stored before the next
-template <int PART> static void divrem_part(uint32_t* out, uint32_t height, uint32_t row, bool live, const tg::Ev& e, const tg::DivRemVals& d) {
-    tg::Row<tg::DIVREM_WIDTH> r;
-    for (int c = 0; c < tg::DIVREM_WIDTH; c++) r.c[c] = 0;
-    if (live) tg::fill_divrem<PART>(r, e, d); else tg::fill_divrem_padding<PART>(r);
-    put_row(out, height, row, r, tg::divrem_part_at(PART), tg::divrem_part_at(PART + 1));
-}
-
+// what the kernels do for their lanes, as a host loop: tg::host_rows (tg_row_kernel.hpp), and for DivRem the kernel's own body
 static void host_rows(int chip, uint32_t* out, uint32_t height, const uint64_t* in, uint32_t n) {
-    for (uint32_t row = 0; row < height; row++) {
-        const bool live = row < n;
-        if (chip == DIVREM) {
-            tg::Ev e = {};
-            if (live) memcpy(&e, in + (size_t)row * 11, sizeof e);
-            const tg::DivRemVals d = tg::divrem_values(e);
-            divrem_part<0>(out, height, row, live, e, d);
-            divrem_part<1>(out, height, row, live, e, d);
-            divrem_part<2>(out, height, row, live, e, d);
-            divrem_part<3>(out, height, row, live, e, d);
-        } else if (chip == ALU_X0) {
-            tg::Row<tg::ALU_X0_WIDTH> r;
-            for (int c = 0; c < tg::ALU_X0_WIDTH; c++) r.c[c] = 0;
-            if (live) { tg::Ev e; memcpy(&e, in + (size_t)row * 11, sizeof e); tg::fill_alu_x0(r, e); }
-            put_row(out, height, row, r, 0, tg::ALU_X0_WIDTH);
-        } else {
-            tg::Row<tg::MEMORY_LOCAL_WIDTH> r;
-            for (int c = 0; c < tg::MEMORY_LOCAL_WIDTH; c++) r.c[c] = 0;
-            if (live) tg::fill_memory_local(r, in + (size_t)row * tg::MEMORY_LOCAL_RECORD_WORDS);
-            put_row(out, height, row, r, 0, tg::MEMORY_LOCAL_WIDTH);
-        }
-    }
+    const tg::Ev* ev = reinterpret_cast<const tg::Ev*>(in);
+    if (chip == DIVREM) for (uint32_t row = 0; row < height; row++) tg::divrem_row(out, height, ev, n, row);
+    else if (chip == ALU_X0) tg::host_rows<tg::AluX0>(out, height, ev, n);
+    else tg::host_rows<tg::MemoryLocal>(out, height, in, n, (int32_t*)nullptr);
 }
 
 static void put(const char* chip, const char* key, int v) { printf("%s %s %d\n", chip, key, v); }
@@ -143,29 +110,6 @@ static int usage(const char* me) {
     return 1;
 }
 
-// the whole file as u64 words; false when it is not a whole number of `record_words`-word records
-static bool read_records(const char* path, size_t record_words, std::vector<uint64_t>& words) {
-    FILE* f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot open %s\n", path); return false; }
-    uint64_t buf[1024];
-    size_t got, bytes = 0;
-    while ((got = fread(buf, 1, sizeof buf, f)) > 0) {
-        if (got % 8) { bytes = 1; break; }
-        words.insert(words.end(), buf, buf + got / 8);
-    }
-    fclose(f);
-    if (bytes || words.size() % record_words) { fprintf(stderr, "%s is not a whole number of %zu-byte records\n", path, record_words * 8); return false; }
-    return true;
-}
-
-static int write_out(const char* path, const void* data, size_t bytes) {
-    FILE* g = fopen(path, "wb");
-    if (!g) { fprintf(stderr, "cannot open %s\n", path); return 1; }
-    const size_t wrote = bytes ? fwrite(data, 1, bytes, g) : 0;
-    if (fclose(g) != 0 || wrote != bytes) { fprintf(stderr, "short write\n"); return 1; }
-    return 0;
-}
-
 int main(int argc, char** argv) {
     if (argc < 3) return usage(argv[0]);
     const char* what = argv[2];
@@ -178,25 +122,21 @@ int main(int argc, char** argv) {
     if (argc == 5 && !strcmp(what, "global")) {
         std::vector<uint64_t> rec;
         if (!read_records(argv[3], tg::MEMORY_LOCAL_RECORD_WORDS, rec)) return 1;
-        const size_t n = rec.size() / tg::MEMORY_LOCAL_RECORD_WORDS;
-        std::vector<int32_t> ev(n * 2 * tg::GLOBAL_EVENT_WORDS);
-        for (size_t i = 0; i < n; i++) tg::memory_local_global_events(ev.data() + i * 2 * tg::GLOBAL_EVENT_WORDS, rec.data() + i * tg::MEMORY_LOCAL_RECORD_WORDS);
+        const uint32_t n = (uint32_t)(rec.size() / tg::MEMORY_LOCAL_RECORD_WORDS);
+        std::vector<int32_t> ev((size_t)n * 2 * tg::GLOBAL_EVENT_WORDS);
+        std::vector<uint32_t> table((size_t)tg::MEMORY_LOCAL_WIDTH * n);       // the events come with the rows
+        tg::host_rows<tg::MemoryLocal>(table.data(), n, rec.data(), n, ev.data());
         return write_out(argv[4], ev.data(), ev.size() * 4);
     }
     if (strcmp(what, "rows") || argc != 7) return usage(argv[0]);
     int chip = -1;
     for (int k = 0; k < N_CORE_CHIPS; k++) if (!strcmp(argv[3], NAMES[k])) chip = k;
     if (chip < 0) { fprintf(stderr, "unknown chip %s\n", argv[3]); return 1; }
-    char* end = nullptr;
-    const long height_arg = strtol(argv[5], &end, 10);
-    if (*end || end == argv[5] || height_arg < 0 || height_arg > (1l << 20)) { fprintf(stderr, "bad height %s: need 0 <= height <= 2^20\n", argv[5]); return 1; }
-    const uint32_t height = (uint32_t)height_arg;
+    uint32_t height, n;
     std::vector<uint64_t> in;
-    if (!read_records(argv[4], RECORD_WORDS[chip], in)) return 1;
-    const size_t n = in.size() / RECORD_WORDS[chip];
-    if (n > height) { fprintf(stderr, "more than height = %u records\n", height); return 1; }
+    if (!read_rows_input(argv[5], argv[4], RECORD_WORDS[chip], height, in, n)) return 1;
     std::vector<uint32_t> out((size_t)WIDTHS[chip] * height, 0xeeeeeeeeu);
-    host_rows(chip, out.data(), height, in.data(), (uint32_t)n);
+    host_rows(chip, out.data(), height, in.data(), n);
     if (write_out(argv[6], out.data(), out.size() * 4)) return 1;
     fprintf(stderr, "riscv_core_rows host rows %s: %d x %u words\n", NAMES[chip], WIDTHS[chip], height);
     return 0;

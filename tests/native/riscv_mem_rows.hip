@@ -11,16 +11,9 @@
 //   riscv_mem_rows host width                         "chip width" lines
 //
 // Build (done by __graft_entry__.build()): hipcc --offload-arch=gfx950 -O3 -std=c++17 -Isp1_amd/csrc -Iinclude ...
-#include <dlfcn.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
-#include <unistd.h>
 
-#include <string>
-#include <vector>
-
+#include "rows_io.hpp"
 #include "sp1hip.h"
 #include "tg_riscv_mem_rows.hpp"
 
@@ -30,69 +23,15 @@ static_assert(sizeof(tg::MemEv) == sizeof(sp1hip_rv64_mem_event_t), "event layou
 static const char* const NAMES[tg::N_MEM_CHIPS] = {"LoadByte", "LoadHalf", "LoadWord", "LoadDouble", "LoadX0", "StoreByte", "StoreHalf", "StoreWord",
                                                    "StoreDouble"};
 
-// what tracegen_mem_kernel does for its lane, as a host loop: the zero row, fill_mem_row for an event's row, one Montgomery word
-// per column
-template <int CHIP> static void host_rows(uint32_t* out, uint32_t height, const tg::MemEv* events, uint32_t n) {
-    constexpr int W = tg::mem_width_of(CHIP);
-    for (uint32_t row = 0; row < height; row++) {
-        tg::Row<W> r;
-        for (int c = 0; c < W; c++) r.c[c] = 0;
-        if (row < n) tg::fill_mem_row<CHIP>(r, events[row]);
-        for (int c = 0; c < W; c++) out[(size_t)c * height + row] = r.c[c] ? kb::to_monty(r.c[c]) : 0u;
-    }
-}
-
+// what the kernel does for its lanes, as a host loop: tg::host_rows (tg_row_kernel.hpp)
 static void host_rows_of(int chip, uint32_t* out, uint32_t height, const tg::MemEv* events, uint32_t n) {
     switch (chip) {
-#define ROWS(C) case tg::C: host_rows<tg::C>(out, height, events, n); break
+#define ROWS(C) case tg::C: tg::host_rows<tg::LoadStoreChip<tg::C>>(out, height, events, n); break
         ROWS(LOAD_BYTE); ROWS(LOAD_HALF); ROWS(LOAD_WORD); ROWS(LOAD_DOUBLE); ROWS(LOAD_X0);
         ROWS(STORE_BYTE); ROWS(STORE_HALF); ROWS(STORE_WORD); ROWS(STORE_DOUBLE);
 #undef ROWS
     }
 }
-
-#if defined(__HIPCC__)
-#define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); return 2; } } while (0)
-
-// the library of the tree this program stands in: tests/native/riscv_mem_rows -> sp1_amd/lib/libsp1hip.so
-static std::string library_path() {
-    char exe[4096];
-    const ssize_t len = readlink("/proc/self/exe", exe, sizeof exe - 1);
-    if (len <= 0) return "";
-    std::string p(exe, (size_t)len);
-    for (int up = 0; up < 3; up++) {
-        const size_t cut = p.rfind('/');
-        if (cut == std::string::npos) return "";
-        p.resize(cut);
-    }
-    return p + "/sp1_amd/lib/libsp1hip.so";
-}
-
-static int device_rows_of(int chip, std::vector<uint32_t>& out, uint32_t height, const std::vector<tg::MemEv>& events) {
-    const std::string path = library_path();
-    void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-    if (!lib) { fprintf(stderr, "cannot load %s: %s\n", path.c_str(), dlerror()); return 2; }
-    using Fn = int (*)(int, uint32_t*, uint32_t, const sp1hip_rv64_mem_event_t*, uint32_t, sp1hip_stream_t);
-    using Err = const char* (*)();
-    const Fn run = (Fn)dlsym(lib, "sp1hip_tracegen_riscv_mem");
-    const Err last_error = (Err)dlsym(lib, "sp1hip_last_error");
-    if (!run) { fprintf(stderr, "%s has no sp1hip_tracegen_riscv_mem\n", path.c_str()); return 2; }
-    void* d_ev = nullptr;
-    uint32_t* d_out = nullptr;
-    const size_t ev_bytes = events.size() * sizeof(tg::MemEv);
-    CHECK(hipMalloc(&d_ev, ev_bytes + 8));
-    CHECK(hipMalloc(&d_out, out.size() * 4 + 8));
-    CHECK(hipMemcpy(d_ev, events.data(), ev_bytes, hipMemcpyHostToDevice));
-    CHECK(hipMemset(d_out, 0xee, out.size() * 4 + 8));
-    const int st = run(chip, d_out, height, (const sp1hip_rv64_mem_event_t*)d_ev, (uint32_t)events.size(), nullptr);
-    if (st != 0) { fprintf(stderr, "sp1hip_tracegen_riscv_mem: %d %s\n", st, last_error ? last_error() : ""); return 2; }
-    CHECK(hipDeviceSynchronize());
-    CHECK(hipMemcpy(out.data(), d_out, out.size() * 4, hipMemcpyDeviceToHost));
-    CHECK(hipFree(d_ev));
-    CHECK(hipFree(d_out));
-    return 0;
-}
-#endif
 
 static void put(const char* chip, const char* key, int v) { printf("%s %s %d\n", chip, key, v); }
 
@@ -160,34 +99,18 @@ int main(int argc, char** argv) {
     char* end = nullptr;
     const long chip = strtol(argv[3], &end, 10);
     if (*end || end == argv[3] || chip < 0 || chip >= tg::N_MEM_CHIPS) { fprintf(stderr, "unknown chip %s\n", argv[3]); return 1; }
-    const long height_arg = strtol(argv[5], &end, 10);
-    if (*end || end == argv[5] || height_arg < 0 || height_arg > (1l << 20)) { fprintf(stderr, "bad height %s: need 0 <= height <= 2^20\n", argv[5]); return 1; }
-    const uint32_t height = (uint32_t)height_arg;
-    FILE* f = fopen(argv[4], "rb");
-    if (!f) { fprintf(stderr, "cannot open %s\n", argv[4]); return 1; }
-    std::vector<tg::MemEv> events;
-    {
-        tg::MemEv e;
-        size_t got;
-        while ((got = fread(&e, 1, sizeof e, f)) == sizeof e) {
-            if (events.size() == height) { fprintf(stderr, "more than height = %u events\n", height); fclose(f); return 1; }
-            events.push_back(e);
-        }
-        fclose(f);
-        if (got != 0) { fprintf(stderr, "the event file is not a whole number of %zu-byte records\n", sizeof e); return 1; }
-    }
+    uint32_t height, n;
+    std::vector<uint64_t> words;
+    if (!read_rows_input(argv[5], argv[4], sizeof(tg::MemEv) / 8, height, words, n)) return 1;
     const int width = tg::mem_width_of((int)chip);
     std::vector<uint32_t> out((size_t)width * height, 0xeeeeeeeeu);
     int st = 0;
-    if (host) host_rows_of((int)chip, out.data(), height, events.data(), (uint32_t)events.size());
+    if (host) host_rows_of((int)chip, out.data(), height, reinterpret_cast<const tg::MemEv*>(words.data()), n);
 #if defined(__HIPCC__)
-    else if (height) st = device_rows_of((int)chip, out, height, events);
+    else if (height) st = device_rows("sp1hip_tracegen_riscv_mem", (int)chip, out, height, words, n);
 #endif
     if (st) return st;
-    FILE* g = fopen(argv[6], "wb");
-    if (!g) { fprintf(stderr, "cannot open %s\n", argv[6]); return 1; }
-    const size_t bytes = out.size() * 4, wrote = bytes ? fwrite(out.data(), 1, bytes, g) : 0;
-    if (fclose(g) != 0 || wrote != bytes) { fprintf(stderr, "short write\n"); return 1; }
+    if (write_out(argv[6], out.data(), out.size() * 4)) return 1;
     fprintf(stderr, "riscv_mem_rows %s rows %s: %d x %u words\n", form, NAMES[chip], width, height);
     return 0;
 }

@@ -15,21 +15,13 @@
 //   riscv_memglobal_rows host width                              "chip width" lines
 //
 // Build (done by __graft_entry__.build()): hipcc --offload-arch=gfx950 -O3 -std=c++17 -Isp1_amd/csrc -Iinclude ...
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
-#include <vector>
-
+#include "rows_io.hpp"
 #include "sp1hip.h"
 #include "tg_riscv_memglobal_rows.hpp"
 
 namespace tg = sp1hip::tg;
-
-template <int W> static void put_row(uint32_t* out, uint32_t height, uint32_t row, const tg::Row<W>& r) {
-    for (int c = 0; c < W; c++) out[(size_t)c * height + row] = r.c[c] ? kb::to_monty(r.c[c]) : 0u;
-}
 
 static void put(const char* chip, const char* key, int v) { printf("%s %s %d\n", chip, key, v); }
 
@@ -56,29 +48,6 @@ static int usage(const char* me) {
     fprintf(stderr, "usage: %s host rows CHIP IN HEIGHT OUT ARGS...\n       %s host global CHIP IN OUT ARGS...\n"
                     "       %s host records IN WORDS_PER_EVENT OUT SEGMENT...\n       %s host layout|width\n", me, me, me, me);
     return 1;
-}
-
-// the whole file as u64 words; false when it is not a whole number of `record_words`-word records
-static bool read_records(const char* path, size_t record_words, std::vector<uint64_t>& words) {
-    FILE* f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot open %s\n", path); return false; }
-    uint64_t buf[1024];
-    size_t got, bytes = 0;
-    while ((got = fread(buf, 1, sizeof buf, f)) > 0) {
-        if (got % 8) { bytes = 1; break; }
-        words.insert(words.end(), buf, buf + got / 8);
-    }
-    fclose(f);
-    if (bytes || words.size() % record_words) { fprintf(stderr, "%s is not a whole number of %zu-byte records\n", path, record_words * 8); return false; }
-    return true;
-}
-
-static int write_out(const char* path, const void* data, size_t bytes) {
-    FILE* g = fopen(path, "wb");
-    if (!g) { fprintf(stderr, "cannot open %s\n", path); return 1; }
-    const size_t wrote = bytes ? fwrite(data, 1, bytes, g) : 0;
-    if (fclose(g) != 0 || wrote != bytes) { fprintf(stderr, "short write\n"); return 1; }
-    return 0;
 }
 
 static bool number(const char* s, long long lo, long long hi, long long& v) {
@@ -111,6 +80,13 @@ static bool parse_chip(const char* name, char** args, int n_args, bool with_prev
     c.arg2_word = (int)v;
     return true;
 }
+
+// what the kernels do for their lanes, as a host loop: tg::host_rows (tg_row_kernel.hpp); `global_events` may be null
+static void host_rows(const Chip& chip, uint32_t* out, uint32_t height, const uint64_t* in, uint32_t n, int32_t* global_events) {
+    if (chip.kind == 2) tg::host_rows<tg::SyscallPrecompile>(out, height, in, n, chip.words, chip.syscall_id, chip.arg2_word, global_events);
+    else tg::host_rows<tg::MemoryGlobal>(out, height, in, n, chip.previous, chip.kind, global_events);
+}
+static int width_of(const Chip& chip) { return chip.kind == 2 ? tg::SYSCALL_PRECOMPILE_WIDTH : tg::MEMORY_GLOBAL_WIDTH; }
 
 int main(int argc, char** argv) {
     if (argc < 3) return usage(argv[0]);
@@ -153,42 +129,21 @@ int main(int argc, char** argv) {
         if (!parse_chip(argv[3], argv + 6, argc - 6, false, chip)) return usage(argv[0]);
         std::vector<uint64_t> in;
         if (!read_records(argv[4], chip.words, in)) return 1;
-        const size_t n = in.size() / chip.words;
-        std::vector<int32_t> ev(n * tg::GLOBAL_EVENT_WORDS);
-        for (size_t i = 0; i < n; i++) {
-            int32_t* o = ev.data() + i * tg::GLOBAL_EVENT_WORDS;
-            if (chip.kind == 2) tg::syscall_precompile_global_event(o, in.data() + i * chip.words, chip.syscall_id, chip.arg2_word);
-            else tg::memory_global_event(o, in.data() + i * chip.words, chip.kind == 1);
-        }
+        const uint32_t n = (uint32_t)(in.size() / chip.words);
+        std::vector<int32_t> ev((size_t)n * tg::GLOBAL_EVENT_WORDS);
+        std::vector<uint32_t> table((size_t)width_of(chip) * n);               // the events come with the rows
+        host_rows(chip, table.data(), n, in.data(), n, ev.data());
         return write_out(argv[5], ev.data(), ev.size() * 4);
     }
     if (strcmp(what, "rows") || argc < 7) return usage(argv[0]);
     Chip chip;
     if (!parse_chip(argv[3], argv + 7, argc - 7, true, chip)) return usage(argv[0]);
-    if (!number(argv[5], 0, 1ll << 20, v)) return 1;
-    const uint32_t height = (uint32_t)v;
+    uint32_t height, n;
     std::vector<uint64_t> in;
-    if (!read_records(argv[4], chip.words, in)) return 1;
-    const size_t n = in.size() / chip.words;
-    if (n > height) { fprintf(stderr, "more than height = %u records\n", height); return 1; }
-    const int width = chip.kind == 2 ? tg::SYSCALL_PRECOMPILE_WIDTH : tg::MEMORY_GLOBAL_WIDTH;
+    if (!read_rows_input(argv[5], argv[4], chip.words, height, in, n)) return 1;
+    const int width = width_of(chip);
     std::vector<uint32_t> out((size_t)width * height, 0xeeeeeeeeu);
-    for (uint32_t row = 0; row < height; row++) {               // what the kernels do for their lane
-        if (chip.kind == 2) {
-            tg::Row<tg::SYSCALL_PRECOMPILE_WIDTH> r;
-            for (int c = 0; c < tg::SYSCALL_PRECOMPILE_WIDTH; c++) r.c[c] = 0;
-            if (row < n) tg::fill_syscall_precompile(r, in.data() + (size_t)row * chip.words, chip.syscall_id, chip.arg2_word);
-            put_row(out.data(), height, row, r);
-        } else {
-            tg::Row<tg::MEMORY_GLOBAL_WIDTH> r;
-            for (int c = 0; c < tg::MEMORY_GLOBAL_WIDTH; c++) r.c[c] = 0;
-            if (row < n) {
-                const uint64_t prev = row ? in[(size_t)(row - 1) * tg::MEMORY_GLOBAL_RECORD_WORDS] : chip.previous;
-                tg::fill_memory_global(r, in.data() + (size_t)row * tg::MEMORY_GLOBAL_RECORD_WORDS, prev, row);
-            }
-            put_row(out.data(), height, row, r);
-        }
-    }
+    host_rows(chip, out.data(), height, in.data(), n, nullptr);
     if (write_out(argv[6], out.data(), out.size() * 4)) return 1;
     fprintf(stderr, "riscv_memglobal_rows host rows %s: %d x %u words\n", argv[3], width, height);
     return 0;

@@ -15,13 +15,9 @@
 //   riscv_sys_rows host bins                          "bin words" lines
 //
 // Build (done by __graft_entry__.build()): hipcc --offload-arch=gfx950 -O3 -std=c++17 -Isp1_amd/csrc -Iinclude ...
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
-#include <vector>
-
+#include "rows_io.hpp"
 #include "sp1hip.h"
 #include "tg_riscv_sys_rows.hpp"
 #include "tg_rv64_partition.hpp"
@@ -36,25 +32,13 @@ static const char* const NAMES[N_SYS_CHIPS] = {"SyscallInstrs", "SyscallCore", "
 static const int WIDTHS[N_SYS_CHIPS] = {tg::SYSCALL_INSTRS_WIDTH, tg::SYSCALL_CORE_WIDTH, tg::STATE_BUMP_WIDTH, tg::MEMORY_BUMP_WIDTH};
 static const size_t RECORD_WORDS[N_SYS_CHIPS] = {11, 11, tg::STATE_BUMP_RECORD_WORDS, tg::MEMORY_BUMP_RECORD_WORDS};
 
-template <int W> static void put_row(uint32_t* out, uint32_t height, uint32_t row, const tg::Row<W>& r) {
-    for (int c = 0; c < W; c++) out[(size_t)c * height + row] = r.c[c] ? kb::to_monty(r.c[c]) : 0u;
-}
-
-template <int W, class Fill> static void rows_of(uint32_t* out, uint32_t height, uint32_t n, Fill fill) {
-    for (uint32_t row = 0; row < height; row++) {
-        tg::Row<W> r;
-        for (int c = 0; c < W; c++) r.c[c] = 0;
-        if (row < n) fill(r, row);
-        put_row(out, height, row, r);
-    }
-}
-
+// what the kernels do for their lanes, as a host loop: tg::host_rows (tg_row_kernel.hpp)
 static void host_rows(int chip, uint32_t* out, uint32_t height, const uint64_t* in, uint32_t n) {
-    auto ev = [&](uint32_t row) { tg::Ev e; memcpy(&e, in + (size_t)row * 11, sizeof e); return e; };
-    if (chip == SYSCALL_INSTRS) rows_of<tg::SYSCALL_INSTRS_WIDTH>(out, height, n, [&](auto& r, uint32_t row) { tg::fill_syscall_instrs(r, ev(row)); });
-    else if (chip == SYSCALL_CORE) rows_of<tg::SYSCALL_CORE_WIDTH>(out, height, n, [&](auto& r, uint32_t row) { tg::fill_syscall_core(r, ev(row)); });
-    else if (chip == STATE_BUMP) rows_of<tg::STATE_BUMP_WIDTH>(out, height, n, [&](auto& r, uint32_t row) { tg::fill_state_bump(r, in + (size_t)row * 4); });
-    else rows_of<tg::MEMORY_BUMP_WIDTH>(out, height, n, [&](auto& r, uint32_t row) { tg::fill_memory_bump(r, in + (size_t)row * 4); });
+    const tg::Ev* ev = reinterpret_cast<const tg::Ev*>(in);
+    if (chip == SYSCALL_INSTRS) tg::host_rows<tg::SyscallInstrs>(out, height, ev, n);
+    else if (chip == SYSCALL_CORE) tg::host_rows<tg::SyscallCore>(out, height, ev, n, (int32_t*)nullptr);
+    else if (chip == STATE_BUMP) tg::host_rows<tg::StateBump>(out, height, in, n);
+    else tg::host_rows<tg::MemoryBump>(out, height, in, n);
 }
 
 // the partition by its definition: every event in order, each record appended to its bin
@@ -139,29 +123,6 @@ static int usage(const char* me) {
     return 1;
 }
 
-// the whole file as u64 words; false when it is not a whole number of `record_words`-word records
-static bool read_records(const char* path, size_t record_words, std::vector<uint64_t>& words) {
-    FILE* f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot open %s\n", path); return false; }
-    uint64_t buf[1024];
-    size_t got, bytes = 0;
-    while ((got = fread(buf, 1, sizeof buf, f)) > 0) {
-        if (got % 8) { bytes = 1; break; }
-        words.insert(words.end(), buf, buf + got / 8);
-    }
-    fclose(f);
-    if (bytes || words.size() % record_words) { fprintf(stderr, "%s is not a whole number of %zu-byte records\n", path, record_words * 8); return false; }
-    return true;
-}
-
-static int write_out(const char* path, const void* data, size_t bytes) {
-    FILE* g = fopen(path, "wb");
-    if (!g) { fprintf(stderr, "cannot open %s\n", path); return 1; }
-    const size_t wrote = bytes ? fwrite(data, 1, bytes, g) : 0;
-    if (fclose(g) != 0 || wrote != bytes) { fprintf(stderr, "short write\n"); return 1; }
-    return 0;
-}
-
 int main(int argc, char** argv) {
     if (argc < 3) return usage(argv[0]);
     const char* what = argv[2];
@@ -188,29 +149,21 @@ int main(int argc, char** argv) {
     if (argc == 5 && !strcmp(what, "global")) {
         std::vector<uint64_t> rec;
         if (!read_records(argv[3], 11, rec)) return 1;
-        const size_t n = rec.size() / 11;
-        std::vector<int32_t> ev(n * tg::GLOBAL_EVENT_WORDS);
-        for (size_t i = 0; i < n; i++) {
-            tg::Ev e;
-            memcpy(&e, rec.data() + i * 11, sizeof e);
-            tg::syscall_core_global_event(ev.data() + i * tg::GLOBAL_EVENT_WORDS, e);
-        }
+        const uint32_t n = (uint32_t)(rec.size() / 11);
+        std::vector<int32_t> ev((size_t)n * tg::GLOBAL_EVENT_WORDS);
+        std::vector<uint32_t> table((size_t)tg::SYSCALL_CORE_WIDTH * n);       // the events come with the rows
+        tg::host_rows<tg::SyscallCore>(table.data(), n, reinterpret_cast<const tg::Ev*>(rec.data()), n, ev.data());
         return write_out(argv[4], ev.data(), ev.size() * 4);
     }
     if (strcmp(what, "rows") || argc != 7) return usage(argv[0]);
     int chip = -1;
     for (int k = 0; k < N_SYS_CHIPS; k++) if (!strcmp(argv[3], NAMES[k])) chip = k;
     if (chip < 0) { fprintf(stderr, "unknown chip %s\n", argv[3]); return 1; }
-    char* end = nullptr;
-    const long height_arg = strtol(argv[5], &end, 10);
-    if (*end || end == argv[5] || height_arg < 0 || height_arg > (1l << 20)) { fprintf(stderr, "bad height %s: need 0 <= height <= 2^20\n", argv[5]); return 1; }
-    const uint32_t height = (uint32_t)height_arg;
+    uint32_t height, n;
     std::vector<uint64_t> in;
-    if (!read_records(argv[4], RECORD_WORDS[chip], in)) return 1;
-    const size_t n = in.size() / RECORD_WORDS[chip];
-    if (n > height) { fprintf(stderr, "more than height = %u records\n", height); return 1; }
+    if (!read_rows_input(argv[5], argv[4], RECORD_WORDS[chip], height, in, n)) return 1;
     std::vector<uint32_t> out((size_t)WIDTHS[chip] * height, 0xeeeeeeeeu);
-    host_rows(chip, out.data(), height, in.data(), (uint32_t)n);
+    host_rows(chip, out.data(), height, in.data(), n);
     if (write_out(argv[6], out.data(), out.size() * 4)) return 1;
     fprintf(stderr, "riscv_sys_rows host rows %s: %d x %u words\n", NAMES[chip], WIDTHS[chip], height);
     return 0;

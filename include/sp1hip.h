@@ -705,6 +705,43 @@ int sp1hip_tracegen_riscv_secp256k1_add(uint32_t* d_table, uint32_t height, cons
 int sp1hip_tracegen_riscv_secp256k1_double(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events,
                                            sp1hip_stream_t stream);
 
+/* Device trace generation for the four chips of the SHA_EXTEND and SHA_COMPRESS precompile shards, from the executor's event records
+ * as they are (sp1hip_rv64_sha_extend_events: n_events x 786 u64 on the device — [0] clk, [1] w_ptr, [2 + 11 r ..] step r < 48: four
+ * (previous timestamp, word read) pairs for w[i-15], w[i-2], w[i-16], w[i-7], then w[i]'s previous timestamp, previous value and new
+ * value, [530 + 4 k ..] word k < 64 of w: initial timestamp, initial value, final timestamp, final value;
+ * sp1hip_rv64_sha_compress_events: 155 u64 — [0] clk, [1] w_ptr, [2] h_ptr, [3 + 2 q] / [4 + 2 q] the previous timestamp and the word
+ * read of h word q < 8, [19 + 2 t] / [20 + 2 t] the same of w word t < 64, [147 + q] the h word written). The reference fills the four
+ * tables on the host (crates/core/machine/src/syscall/precompiles/sha256/extend/{trace,controller}.rs, compress/{trace,controller}.rs)
+ * and has no device filler for them. Output as above: column-major [width][height] Montgomery words.
+ *   sp1hip_tracegen_riscv_sha_extend            ShaExtend, width 128: row 48 e + r is step i = 16 + r of event e, at clk + 1 + r — clk_high,
+ *       clk_low + 1, next_clk, w_ptr[3], five AddrAddOperation values, i, the accesses of w[i-15], w[i-2], w[i-16], w[i-7] and w[i], the
+ *       fixed rotates and shifts of w[i-15] and w[i-2], s0, s1 with their intermediates, s2, is_real. Padding rows are zero. Needs
+ *       48 n_events <= height.
+ *   sp1hip_tracegen_riscv_sha_extend_control    ShaExtendControl, width 18: one row per event; zero padding rows.
+ *   sp1hip_tracegen_riscv_sha_compress          ShaCompress, width 206: row 80 e + j of event e — j < 8 reads h[j] at clk, 8 <= j < 72 is
+ *       round j - 8 and reads w[j - 8] at clk + 1, j >= 72 writes h[j - 72] at clk + 2. The working state entering the row is computed
+ *       from the h and w words read. The compression column groups are zero off the compression rows, the finalise groups off the
+ *       finalise rows. A PADDING ROW IS NOT ZERO: octet, octet_num, index and k cycle by row mod 80 on every row of the table; every
+ *       other column of a padding row is zero. Needs 80 n_events <= height.
+ *   sp1hip_tracegen_riscv_sha_compress_control  ShaCompressControl, width 53: one row per event — clk, two SyscallAddrOperation, the two
+ *       slice ends, is_real, the state read and the state after the 64 rounds; zero padding rows.
+ * The MemoryLocal records of the touched words: sp1hip_precompile_local_records with { 2, 8, 3, 147, 2 } and { 1, 64, 19, none, 1 } for
+ * SHA_COMPRESS (155 words; arg2_word 2) and with the QUAD form { 1, 64, 530, 0xFFFFFFFE, 0 } for SHA_EXTEND (786 words): final_word =
+ * 0xFFFFFFFE reads word i's initial clk, initial value, final clk and final value from ev[pairs_word + 4 i .. + 4 i + 3] — the words
+ * of one SHA_EXTEND call end at different timestamps — and needs pairs_word + 4 count <= words_per_event; final_clk_delta is not read.
+ * All argument checks come before any launch; a null pointer is accepted only with a zero count / height; height == 0 succeeds
+ * without a launch. The calls enqueue and return: they do not synchronise. */
+int sp1hip_tracegen_riscv_sha_extend_width(void);            /* 128 */
+int sp1hip_tracegen_riscv_sha_extend_control_width(void);    /* 18 */
+int sp1hip_tracegen_riscv_sha_compress_width(void);          /* 206 */
+int sp1hip_tracegen_riscv_sha_compress_control_width(void);  /* 53 */
+int sp1hip_tracegen_riscv_sha_extend(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_sha_extend_control(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events,
+                                             sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_sha_compress(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_sha_compress_control(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events,
+                                               sp1hip_stream_t stream);
+
 /* The Byte, Range and Program multiplicities of a shard, counted on the device from the tables that send: the receive side of the
  * byte lookup argument, which the reference computes in `generate_dependencies` of its Byte and Range chips
  * (crates/core/machine/src/bytes/trace.rs:L50-L66, range/trace.rs:L54-L95), and the Program chip's count of executed pcs. Generic over

@@ -274,6 +274,14 @@ PROTOTYPES = [
     ("sp1hip_tracegen_riscv_secp256k1_double_width", None, []),
     ("sp1hip_tracegen_riscv_secp256k1_add", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_secp256k1_double", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_sha_extend_width", None, []),
+    ("sp1hip_tracegen_riscv_sha_extend_control_width", None, []),
+    ("sp1hip_tracegen_riscv_sha_compress_width", None, []),
+    ("sp1hip_tracegen_riscv_sha_compress_control_width", None, []),
+    ("sp1hip_tracegen_riscv_sha_extend", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_sha_extend_control", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_sha_compress", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_sha_compress_control", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_lookup_count_sends", None, [u32p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, _vp]),
     ("sp1hip_lookup_count_program", None, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, _vp, _vp, C.c_uint32, _vp]),
     ("sp1hip_lookup_counts_finish", None, [_vp, C.c_uint64, _vp, _vp, _vp]),

@@ -692,7 +692,8 @@ def tracegen_riscv_syscall_precompile(events, height, syscall_id, arg2_word=-1, 
 def precompile_local_records(events, segments, stream=None):
     """The MemoryLocal records of the words a precompile's calls touched (sp1hip_precompile_local_records): events = a device int64
     tensor [n, words] of event records, segments = up to four (ptr_word, count, pairs_word, final_word or None, final_clk_delta) —
-    PRECOMPILE_DESCRIPTORS has those of Keccak and secp256k1. Returns a device int64 tensor [n * sum of counts, 5] { addr, initial
+    PRECOMPILE_DESCRIPTORS has those of Keccak and secp256k1, SHA_DESCRIPTORS those of SHA-256 (final_word PRECOMPILE_QUAD_WORDS: the
+    quad form). Returns a device int64 tensor [n * sum of counts, 5] { addr, initial
     clk, initial value, final clk, final value }, segment after segment, event by event inside each: what tracegen_riscv_memory_local
     reads."""
     n = int(events.shape[0])
@@ -805,6 +806,43 @@ def tracegen_riscv_secp256k1_double(events, height, stream=None):
     return tracegen_riscv_records("Secp256k1DoubleAssign", events, height, stream)
 
 
+SHA_EXTEND_EVENT_WORDS, SHA_COMPRESS_EVENT_WORDS = 786, 155                        # SP1HIP_RV64_SHA_EXTEND_WORDS, _SHA_COMPRESS_WORDS
+# final_word of a segment of sp1hip_precompile_local_records in the quad form: event words pairs_word + 4 i .. + 4 i + 3 hold word i's
+# initial timestamp, initial value, final timestamp and final value (the words of one SHA_EXTEND call end at different timestamps)
+PRECOMPILE_QUAD_WORDS = 0xFFFFFFFE
+# the SHA-256 kinds in the shape of PRECOMPILE_DESCRIPTORS — what riscv_more_trace.sha_extend_shard_from / sha_compress_shard_from hand
+# _close_precompile_shard: SHA_EXTEND's 64 words of w in the quad form; SHA_COMPRESS's 8 words of h (written at clk + 2), then its
+# 64 words of w (read at clk + 1), arg2 = h_ptr
+SHA_DESCRIPTORS = {"sha_extend": (SHA_EXTEND_EVENT_WORDS, 0x05, -1, ((1, 64, 530, PRECOMPILE_QUAD_WORDS, 0),)),
+                   "sha_compress": (SHA_COMPRESS_EVENT_WORDS, 0x06, 2, ((2, 8, 3, 147, 2), (1, 64, 19, None, 1)))}
+
+
+def tracegen_riscv_sha_extend(events, height, stream=None):
+    """`generate_trace_device` for the ShaExtend chip (sp1hip_tracegen_riscv_sha_extend): events = a device int64 tensor [n, 786] of the
+    executor's SHA_EXTEND records (riscv_exec.ExecutedShard.sha_extend); 48 rows per event, height >= 48 n, zero padding rows. Returns
+    the column-major [128][height] table as a ColMajor."""
+    return tracegen_riscv_records("ShaExtend", events, height, stream)
+
+
+def tracegen_riscv_sha_extend_control(events, height, stream=None):
+    """The same events' ShaExtendControl table (sp1hip_tracegen_riscv_sha_extend_control): one row per event, height >= n;
+    column-major [18][height]."""
+    return tracegen_riscv_records("ShaExtendControl", events, height, stream)
+
+
+def tracegen_riscv_sha_compress(events, height, stream=None):
+    """`generate_trace_device` for the ShaCompress chip (sp1hip_tracegen_riscv_sha_compress): events = a device int64 tensor [n, 155] of
+    the executor's SHA_COMPRESS records (ExecutedShard.sha_compress); 80 rows per event, height >= 80 n. Padding rows keep octet,
+    octet_num, index and k cycling by row mod 80 and are zero elsewhere. Returns the column-major [206][height] table as a ColMajor."""
+    return tracegen_riscv_records("ShaCompress", events, height, stream)
+
+
+def tracegen_riscv_sha_compress_control(events, height, stream=None):
+    """The same events' ShaCompressControl table (sp1hip_tracegen_riscv_sha_compress_control): one row per event, height >= n;
+    column-major [53][height]."""
+    return tracegen_riscv_records("ShaCompressControl", events, height, stream)
+
+
 # chip: (entry point, u64 words of a record, leading chip argument or None) — every chip whose table is made from its record stream
 # alone, the wrappers above by chip name (MemoryLocal, MemoryGlobal*, SyscallCore and SyscallPrecompile also write Global events)
 RISCV_TRACEGEN = {**{c: ("sp1hip_tracegen_riscv_alu", ALU_EVENT_WORDS, k) for c, k in RISCV_ALU_CHIPS.items()},
@@ -816,7 +854,11 @@ RISCV_TRACEGEN = {**{c: ("sp1hip_tracegen_riscv_alu", ALU_EVENT_WORDS, k) for c,
                   "KeccakPermute": ("sp1hip_tracegen_riscv_keccak", KECCAK_EVENT_WORDS, None),
                   "KeccakPermuteControl": ("sp1hip_tracegen_riscv_keccak_control", KECCAK_EVENT_WORDS, None),
                   "Secp256k1AddAssign": ("sp1hip_tracegen_riscv_secp256k1_add", SECP_ADD_EVENT_WORDS, None),
-                  "Secp256k1DoubleAssign": ("sp1hip_tracegen_riscv_secp256k1_double", SECP_DOUBLE_EVENT_WORDS, None)}
+                  "Secp256k1DoubleAssign": ("sp1hip_tracegen_riscv_secp256k1_double", SECP_DOUBLE_EVENT_WORDS, None),
+                  "ShaExtend": ("sp1hip_tracegen_riscv_sha_extend", SHA_EXTEND_EVENT_WORDS, None),
+                  "ShaExtendControl": ("sp1hip_tracegen_riscv_sha_extend_control", SHA_EXTEND_EVENT_WORDS, None),
+                  "ShaCompress": ("sp1hip_tracegen_riscv_sha_compress", SHA_COMPRESS_EVENT_WORDS, None),
+                  "ShaCompressControl": ("sp1hip_tracegen_riscv_sha_compress_control", SHA_COMPRESS_EVENT_WORDS, None)}
 
 
 def tracegen_riscv_records(chip, records, height, stream=None):

@@ -20,6 +20,7 @@ constexpr int MEMORY_GLOBAL_WIDTH = 30, SYSCALL_PRECOMPILE_WIDTH = 10;
 constexpr int MEMORY_GLOBAL_RECORD_WORDS = 3;                 // { addr, value, timestamp }
 constexpr int PRECOMPILE_MAX_SEGMENTS = 4;
 constexpr uint32_t PRECOMPILE_NO_WORD = 0xffffffffu;          // a segment whose words are only read has no final_word
+constexpr uint32_t PRECOMPILE_QUAD_WORDS = 0xfffffffeu;       // final_word of a segment in the quad form: four record words per word
 
 namespace col {
 constexpr int MG_CLK_HIGH = 0, MG_CLK_LOW = 1, MG_INDEX = 2, MG_PREV_ADDR = 3, MG_ADDR = 6, MG_LT_BIT = 9, MG_LT_U16_FLAGS = 10,
@@ -127,17 +128,21 @@ struct SyscallPrecompile : ZeroPaddedChip<SYSCALL_PRECOMPILE_WIDTH, uint64_t> {
 // One run of consecutive words a precompile touches through one pointer: event word ptr_word holds the pointer, `count` words
 // follow it in memory; event words pairs_word + 2 i, + 2 i + 1 hold word i's previous timestamp and value, event word final_word + i
 // the value the call leaves (PRECOMPILE_NO_WORD: the words are only read and keep theirs); the call's last access to them is at
-// clk + final_clk_delta
+// clk + final_clk_delta. The quad form (final_word = PRECOMPILE_QUAD_WORDS) is for a call whose words end at different timestamps
+// (SHA_EXTEND): event words pairs_word + 4 i .. + 4 i + 3 hold word i's initial timestamp, initial value, final timestamp and final
+// value, and final_clk_delta is not read
 struct LocalSegment { uint32_t ptr_word, count, pairs_word, final_word, final_clk_delta; };
 struct LocalSegments { LocalSegment s[PRECOMPILE_MAX_SEGMENTS]; uint32_t n; };
 
 // The MemoryLocal record { addr, initial clk, initial value, final clk, final value } of word i of event `ev` in segment `s`
 TG_HD void precompile_local_record(uint64_t* rec, const uint64_t* ev, const LocalSegment& s, uint32_t i) {
+    const bool quad = s.final_word == PRECOMPILE_QUAD_WORDS;
+    const uint32_t at = s.pairs_word + (quad ? 4 : 2) * i;
     rec[0] = ev[s.ptr_word] + 8ull * i;
-    rec[1] = ev[s.pairs_word + 2 * i];
-    rec[2] = ev[s.pairs_word + 2 * i + 1];
-    rec[3] = ev[0] + s.final_clk_delta;
-    rec[4] = s.final_word == PRECOMPILE_NO_WORD ? rec[2] : ev[s.final_word + i];
+    rec[1] = ev[at];
+    rec[2] = ev[at + 1];
+    rec[3] = quad ? ev[at + 2] : ev[0] + s.final_clk_delta;
+    rec[4] = quad ? ev[at + 3] : s.final_word == PRECOMPILE_NO_WORD ? rec[2] : ev[s.final_word + i];
 }
 
 // Where record `q` of a shard of n_events events comes from: the segments lie one after the other, segment s holding n_events *

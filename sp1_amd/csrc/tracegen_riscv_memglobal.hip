@@ -64,8 +64,9 @@ int sp1hip_precompile_local_records(uint64_t* d_records, uint64_t records_capaci
         const uint32_t* w = segments + 5 * k;
         const tg::LocalSegment s = {w[0], w[1], w[2], w[3], w[4]};
         SP1HIP_REQUIRE(s.count >= 1 && s.count <= words_per_event && s.ptr_word < words_per_event && s.pairs_word <= words_per_event &&
-                       (uint64_t)s.pairs_word + 2ull * s.count <= words_per_event &&
-                       (s.final_word == tg::PRECOMPILE_NO_WORD || (uint64_t)s.final_word + s.count <= words_per_event),
+                       (uint64_t)s.pairs_word + (s.final_word == tg::PRECOMPILE_QUAD_WORDS ? 4ull : 2ull) * s.count <= words_per_event &&
+                       (s.final_word == tg::PRECOMPILE_NO_WORD || s.final_word == tg::PRECOMPILE_QUAD_WORDS ||
+                        (uint64_t)s.final_word + s.count <= words_per_event),
                        "a segment reads behind the event record");
         segs.s[k] = s;
         total += (uint64_t)n_events * s.count;

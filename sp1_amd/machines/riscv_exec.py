@@ -659,18 +659,20 @@ def device_memory_shard(init_addrs, init_recs, fin_addrs, fin_recs, prep, ctx, p
 
 
 DEVICE_PRECOMPILE_KINDS = ("keccak", "secp256k1_add", "secp256k1_double")
+DEVICE_SHA_KINDS = ("sha_extend", "sha_compress")             # their descriptors are api.SHA_DESCRIPTORS
 
 
 def device_precompile_shard(kind, events, prep, ctx, stream=None):
-    """A provable precompile shard of `kind` (DEVICE_PRECOMPILE_KINDS) from the executor's event records alone ([n, 77 / 43 / 26] int64,
-    numpy or torch), every table made ON THE DEVICE: (machine, chips, publics, global events) in the shape of device_core_shard. The
-    wide tables come from api.tracegen_riscv_keccak / _keccak_control / _secp256k1_add / _double; SyscallPrecompile
+    """A provable precompile shard of `kind` (DEVICE_PRECOMPILE_KINDS, DEVICE_SHA_KINDS) from the executor's event records alone ([n, 77 /
+    43 / 26 / 786 / 155] int64, numpy or torch), every table made ON THE DEVICE: (machine, chips, publics, global events) in the shape
+    of device_core_shard. The wide tables come from api.tracegen_riscv_keccak / _keccak_control / _secp256k1_add / _double /
+    _sha_extend / _sha_extend_control / _sha_compress / _sha_compress_control; SyscallPrecompile
     (api.tracegen_riscv_syscall_precompile) and the MemoryLocal records of the touched words (api.precompile_local_records, one
-    record per word of each call) from the same records by api.PRECOMPILE_DESCRIPTORS[kind]; MemoryLocal and Global as in a core
+    record per word of each call) from the same records by api.PRECOMPILE_DESCRIPTORS[kind] or api.SHA_DESCRIPTORS[kind]; MemoryLocal and Global as in a core
     shard — MemoryLocal's two events per record first, then SyscallPrecompile's receives —; the public values are the program's
     initial state with the Global fields set. No Tracer, no host table."""
     from .. import api
-    words, syscall_id, arg2_word, segments = api.PRECOMPILE_DESCRIPTORS[kind]
+    words, syscall_id, arg2_word, segments = (api.SHA_DESCRIPTORS if kind in DEVICE_SHA_KINDS else api.PRECOMPILE_DESCRIPTORS)[kind]
     chip, control, rows_per_call, _ = PRECOMPILES[kind]
     with torch.cuda.stream(stream or torch.cuda.current_stream()):
         ev = _on_device(events, words)
@@ -687,7 +689,7 @@ def device_precompile_shard(kind, events, prep, ctx, stream=None):
         return machine, chips, publics, gev
 
 
-DEVICE_KINDS = ("core", "memory") + DEVICE_PRECOMPILE_KINDS
+DEVICE_KINDS = ("core", "memory") + DEVICE_PRECOMPILE_KINDS + DEVICE_SHA_KINDS
 
 
 def device_shard(executor, rec, prep, stream=None):
@@ -698,7 +700,7 @@ def device_shard(executor, rec, prep, stream=None):
     if rec.kind == "memory":
         return device_memory_shard(rec.init_addrs, rec.init_recs, rec.fin_addrs, rec.fin_recs, prep, rec.ctx, previous_init=rec.previous_init,
                                    previous_fin=rec.previous_fin, stream=stream)
-    if rec.kind in DEVICE_PRECOMPILE_KINDS:
+    if rec.kind in DEVICE_PRECOMPILE_KINDS or rec.kind in DEVICE_SHA_KINDS:
         return device_precompile_shard(rec.kind, rec.events, prep, rec.ctx, stream=stream)
     raise ValueError("no device builder for a %r shard: device_shard makes %s" % (rec.kind, ", ".join(DEVICE_KINDS)))
 

@@ -11,8 +11,10 @@
 //   fixed_at_zero    /root/reference/slop/crates/multilinear/src/restrict.rs:L75-L87
 //   pair leaves      fri.rs:L103-L108 (codeword reshaped [N/2][8]) + p3sync.rs leaf hashing
 //
-// All of these are single-pass streaming kernels: one lane per output row, every column access
+// All of these are single-pass streaming kernels: one lane per output row (four rows and 16-byte
+// accesses in the two that read the whole trace: batch, column evaluations), every column access
 // coalesced, ext vectors in SoA (4 base columns) so a wave reads 4 x 256 B contiguous runs.
+#include "col_dot.hpp"
 #include "device_ctx.hpp"
 #include "tensor_table.hpp"
 
@@ -50,9 +52,42 @@ __global__ void monty_convert_kernel(uint32_t* data, size_t n) {
 // ---------------------------------------------------------------- batch (RLC of all columns)
 // out[r] = sum_g coeff[g] * col_g[r]. Coefficients are wave-uniform (scalar loads); the sum over the columns is
 // accumulated unreduced (kb::DotAcc, total_width <= 2^16).
+// A lane owns four consecutive rows (height % 4 == 0, every column and `out` 16-byte aligned: 16-byte loads and stores) and walks
+// the columns BATCH_STEP at a time, all loads of a step issued before the first multiply-add.
+constexpr uint32_t BATCH_STEP = 4;    // (8: 140 VGPRs, three waves per SIMD)
 __global__ __launch_bounds__(256) void batch_kernel(const uint32_t* const* __restrict__ cols, uint32_t total_width,
                                                     uint32_t height, const uint32_t* __restrict__ coeffs,
                                                     uint32_t* __restrict__ out) {
+    const uint32_t row = (blockIdx.x * 256u + threadIdx.x) * 4u;
+    if (row >= height) return;
+    kb::DotAcc acc[4];                // one per row; delayed reduction as in batch_rows_kernel
+#pragma unroll
+    for (int j = 0; j < 4; j++) kb::dot_init(acc[j]);
+    auto add = [&](uint32_t g, const q4_t& v) {
+        const kb::Ext c{{coeffs[4 * g], coeffs[4 * g + 1], coeffs[4 * g + 2], coeffs[4 * g + 3]}};   // wave-uniform
+#pragma unroll
+        for (int j = 0; j < 4; j++) kb::dot_add(acc[j], c, v[j]);
+    };
+    uint32_t g = 0;
+    for (; g + BATCH_STEP <= total_width; g += BATCH_STEP) {
+        q4_t v[BATCH_STEP];
+#pragma unroll
+        for (uint32_t u = 0; u < BATCH_STEP; u++) v[u] = ld_rows4<true>(cols[g + u], row);
+#pragma unroll
+        for (uint32_t u = 0; u < BATCH_STEP; u++) add(g + u, v[u]);
+    }
+    for (; g < total_width; g++) add(g, ld_rows4<true>(cols[g], row));
+    kb::Ext r[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) r[j] = kb::dot_finish(acc[j]);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        *reinterpret_cast<q4_t*>(out + (size_t)k * height + row) = q4_t{r[0].c[k], r[1].c[k], r[2].c[k], r[3].c[k]};
+}
+// The same with one row per lane and 4-byte accesses: heights below 4 and columns that are not 16-byte aligned.
+__global__ __launch_bounds__(256) void batch_rows_kernel(const uint32_t* const* __restrict__ cols, uint32_t total_width,
+                                                         uint32_t height, const uint32_t* __restrict__ coeffs,
+                                                         uint32_t* __restrict__ out) {
     const uint32_t row = blockIdx.x * 256u + threadIdx.x;
     if (row >= height) return;
     kb::DotAcc acc;                   // delayed reduction: one Montgomery reduction per coordinate for the whole row
@@ -246,42 +281,48 @@ __device__ __forceinline__ void block_sum4(uint32_t (&v)[4], uint32_t* scratch /
     __syncthreads();
 }
 
-constexpr int EVAL_COLS = 4;      // columns per workgroup (4 x 16 VGPRs of unreduced accumulators)
-constexpr int EVAL_ROWS = 16384;  // rows per workgroup
+constexpr int EVAL_COLS = COL_DOT_COLS;        // columns per workgroup (4 x 16 VGPRs of unreduced accumulators)
+constexpr uint32_t EVAL_ROWS = COL_DOT_ROWS;   // rows per workgroup
 
+// NC: the columns of this workgroup (the last one of a launch may have fewer than EVAL_COLS)
+template <int NC>
+__device__ __forceinline__ void eval_columns_group(const uint32_t* const* __restrict__ cols, uint32_t total_width, uint32_t height,
+                                                   const uint32_t* __restrict__ eq, uint32_t* __restrict__ partial,
+                                                   uint32_t (&scratch)[16]) {
+    const uint32_t g0 = blockIdx.x * EVAL_COLS;      // consecutive workgroups share the rows (and their eq slice)
+    const uint32_t r0 = blockIdx.y * EVAL_ROWS, r1 = min(r0 + EVAL_ROWS, height);
+    const uint32_t* col[NC];
+    kb::DotAcc dacc[NC];              // delayed reduction: EVAL_ROWS / 256 terms per lane, one reduction per column
+    bool aligned = aligned16(eq) && (height & 3u) == 0;
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        col[c] = cols[g0 + c];
+        aligned = aligned && aligned16(col[c]);
+        kb::dot_init(dacc[c]);
+    }
+    col_dot_rows<NC>(col, eq, height, r0, r1, aligned, dacc);
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const kb::Ext v = kb::dot_finish(dacc[c]);
+        uint32_t acc[4] = {v.c[0], v.c[1], v.c[2], v.c[3]};
+        block_sum4(acc, scratch);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) partial[((size_t)blockIdx.y * total_width + g0 + c) * 4 + k] = acc[k];
+        }
+    }
+}
 // partial[chunk][g] = sum over the chunk's rows of eq[r] * col_g[r]
 __global__ __launch_bounds__(256) void eval_columns_partial_kernel(const uint32_t* const* __restrict__ cols,
                                                                    uint32_t total_width, uint32_t height,
                                                                    const uint32_t* __restrict__ eq,
                                                                    uint32_t* __restrict__ partial) {
     __shared__ uint32_t scratch[16];
-    const uint32_t g0 = blockIdx.x * EVAL_COLS;      // consecutive workgroups share the rows (and their eq slice)
-    const uint32_t r0 = blockIdx.y * EVAL_ROWS;
-    kb::DotAcc dacc[EVAL_COLS];       // delayed reduction: EVAL_ROWS / 256 terms per lane, one reduction per column
-#pragma unroll
-    for (int c = 0; c < EVAL_COLS; c++) kb::dot_init(dacc[c]);
-    for (uint32_t r = r0 + threadIdx.x; r < r0 + EVAL_ROWS && r < height; r += 256) {
-        kb::Ext e;
-#pragma unroll
-        for (int k = 0; k < 4; k++) e.c[k] = eq[(size_t)k * height + r];
-#pragma unroll
-        for (int c = 0; c < EVAL_COLS; c++)
-            if (g0 + c < total_width) kb::dot_add(dacc[c], e, gptr(cols[g0 + c])[r]);
-    }
-    uint32_t acc[EVAL_COLS][4];
-#pragma unroll
-    for (int c = 0; c < EVAL_COLS; c++) {
-        const kb::Ext v = kb::dot_finish(dacc[c]);
-#pragma unroll
-        for (int k = 0; k < 4; k++) acc[c][k] = v.c[k];
-    }
-#pragma unroll
-    for (int c = 0; c < EVAL_COLS; c++) {
-        block_sum4(acc[c], scratch);
-        if (threadIdx.x == 0 && g0 + c < total_width) {
-#pragma unroll
-            for (int k = 0; k < 4; k++) partial[((size_t)blockIdx.y * total_width + g0 + c) * 4 + k] = acc[c][k];
-        }
+    switch (min(total_width - blockIdx.x * EVAL_COLS, (uint32_t)EVAL_COLS)) {
+        case 1: eval_columns_group<1>(cols, total_width, height, eq, partial, scratch); break;
+        case 2: eval_columns_group<2>(cols, total_width, height, eq, partial, scratch); break;
+        case 3: eval_columns_group<3>(cols, total_width, height, eq, partial, scratch); break;
+        default: eval_columns_group<4>(cols, total_width, height, eq, partial, scratch); break;
     }
 }
 
@@ -536,8 +577,12 @@ int sp1hip_basefold_batch(const sp1hip_tensor_t* tensors, int n_tensors, int lg_
     AsyncScratch cols;
     SP1HIP_TRY(cols.alloc((size_t)tw * sizeof(uint32_t*), s));
     SP1HIP_TRY(expand_columns_async(tab, tw, height, (const uint32_t**)cols.p, s));
-    hipLaunchKernelGGL(batch_kernel, dim3((height + 255) / 256), dim3(256), 0, s, (const uint32_t* const*)cols.p, tw,
-                       height, d_coeffs, d_out);
+    bool aligned = height % 4 == 0 && aligned16(d_out);
+    for (int i = 0; i < tab.n; i++) aligned = aligned && aligned16(tab.base[i]);     // then so is every column
+    if (aligned) hipLaunchKernelGGL(batch_kernel, dim3((height / 4 + 255) / 256), dim3(256), 0, s, (const uint32_t* const*)cols.p, tw,
+                                    height, d_coeffs, d_out);
+    else hipLaunchKernelGGL(batch_rows_kernel, dim3((height + 255) / 256), dim3(256), 0, s, (const uint32_t* const*)cols.p, tw,
+                            height, d_coeffs, d_out);
     SP1HIP_LAUNCH_CHECK();
     return SP1HIP_SUCCESS;
 }

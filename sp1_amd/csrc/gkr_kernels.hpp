@@ -3,6 +3,7 @@
 // gkr_pass_deep_fold) and the trace openings, with the descriptors the host fills for them.
 // Included by gkr.hip only (the prover and its launches; the layout and the shape of the stage are described there).
 #pragma once
+#include "col_dot.hpp"
 #include "device_ctx.hpp"
 #include "round_sync.hpp"
 
@@ -850,28 +851,27 @@ __global__ __launch_bounds__(256) void gkr_pass_deep_fold(const PassDesc* __rest
 
 // ================================================================ trace openings at the final point
 struct OpenDesc { const uint32_t* cols; uint32_t rows, width, col0, out0; };   // one group of <= OPEN_COLS columns of one chip
-constexpr int OPEN_COLS = 4, OPEN_ROWS = 16384;      // (8 columns per workgroup, sharing one read of the eq slice, measured slower: 1.33 vs 0.78 ms)
-// Column sums against eq with delayed reduction (kb::DotAcc): 64 terms per lane, one reduction per column and lane.
-__global__ __launch_bounds__(256) void open_columns_kernel(const OpenDesc* __restrict__ descs, const uint32_t* __restrict__ eq,
-                                                           uint32_t eq_len, uint32_t* __restrict__ partials, uint32_t total_cols) {
-    // consecutive workgroups = the column groups of one table over the SAME rows: their eq slice is re-read from the
-    // caches, not from HBM
-    const OpenDesc d = descs[blockIdx.x];
-    const uint32_t r0 = blockIdx.y * OPEN_ROWS;
-    if (r0 >= d.rows) return;                             // partials are zero-initialised
-    kb::DotAcc acc[OPEN_COLS];
+constexpr int OPEN_COLS = COL_DOT_COLS;              // (8 columns per workgroup, sharing one read of the eq slice, measured slower: 1.33 vs 0.78 ms)
+constexpr uint32_t OPEN_ROWS = COL_DOT_ROWS;
+// Column sums against eq with delayed reduction (kb::DotAcc, col_dot_rows): 64 terms per lane, one reduction per column and lane.
+// NC: the columns of this group (the last group of a table may have fewer than OPEN_COLS).
+template <int NC>
+__device__ __forceinline__ void open_columns_group(const OpenDesc& d, const uint32_t* __restrict__ eq, uint32_t eq_len,
+                                                   uint32_t* __restrict__ partials, uint32_t total_cols, uint32_t (&sm)[4][4 * OPEN_COLS]) {
+    const uint32_t r0 = blockIdx.y * OPEN_ROWS, r1 = min(r0 + OPEN_ROWS, d.rows);
+    const uint32_t* col[NC];
+    kb::DotAcc acc[NC];
+    bool aligned = aligned16(eq) && (eq_len & 3u) == 0;
 #pragma unroll
-    for (int c = 0; c < OPEN_COLS; c++) kb::dot_init(acc[c]);
-    for (uint32_t r = r0 + threadIdx.x; r < r0 + OPEN_ROWS && r < d.rows; r += 256) {
-        const Ext e{{eq[r], eq[eq_len + r], eq[2 * (size_t)eq_len + r], eq[3 * (size_t)eq_len + r]}};
-#pragma unroll
-        for (int c = 0; c < OPEN_COLS; c++)
-            if (d.col0 + c < d.width) kb::dot_add(acc[c], e, gptr(d.cols)[(size_t)(d.col0 + c) * d.rows + r]);
+    for (int c = 0; c < NC; c++) {
+        col[c] = d.cols + (size_t)(d.col0 + c) * d.rows;
+        aligned = aligned && aligned16(col[c]);
+        kb::dot_init(acc[c]);
     }
-    __shared__ uint32_t sm[4][4 * OPEN_COLS];
+    col_dot_rows<NC>(col, eq, eq_len, r0, r1, aligned, acc);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int c = 0; c < OPEN_COLS; c++) {
+    for (int c = 0; c < NC; c++) {
         const Ext v = kb::dot_finish(acc[c]);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -880,13 +880,24 @@ __global__ __launch_bounds__(256) void open_columns_kernel(const OpenDesc* __res
         }
     }
     __syncthreads();
-    if (threadIdx.x < 4 * OPEN_COLS) {
-        const int c = threadIdx.x / 4;
-        if (d.col0 + c < d.width) {
-            uint32_t a = 0;
-            for (int i = 0; i < 4; i++) a = kb::add(a, sm[i][threadIdx.x]);
-            partials[((size_t)blockIdx.y * total_cols + d.out0 + c) * 4 + (threadIdx.x & 3)] = a;
-        }
+    if (threadIdx.x < 4 * NC) {
+        uint32_t a = 0;
+        for (int i = 0; i < 4; i++) a = kb::add(a, sm[i][threadIdx.x]);
+        partials[((size_t)blockIdx.y * total_cols + d.out0) * 4 + threadIdx.x] = a;
+    }
+}
+__global__ __launch_bounds__(256) void open_columns_kernel(const OpenDesc* __restrict__ descs, const uint32_t* __restrict__ eq,
+                                                           uint32_t eq_len, uint32_t* __restrict__ partials, uint32_t total_cols) {
+    // consecutive workgroups = the column groups of one table over the SAME rows: their eq slice is re-read from the
+    // caches, not from HBM
+    __shared__ uint32_t sm[4][4 * OPEN_COLS];
+    const OpenDesc d = descs[blockIdx.x];
+    if (blockIdx.y * OPEN_ROWS >= d.rows) return;         // partials are zero-initialised
+    switch (min(d.width - d.col0, (uint32_t)OPEN_COLS)) {
+        case 1: open_columns_group<1>(d, eq, eq_len, partials, total_cols, sm); break;
+        case 2: open_columns_group<2>(d, eq, eq_len, partials, total_cols, sm); break;
+        case 3: open_columns_group<3>(d, eq, eq_len, partials, total_cols, sm); break;
+        default: open_columns_group<4>(d, eq, eq_len, partials, total_cols, sm); break;
     }
 }
 // out[j] = sum over the chunks of partials[chunk][j]: 64 words per workgroup, four chunk lanes per word folded through LDS

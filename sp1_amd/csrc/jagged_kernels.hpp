@@ -141,6 +141,7 @@ __global__ __launch_bounds__(256) void jg_round0_sum(JgSegs S, JgJ J, uint32_t n
 struct JgTab { const uint32_t* q; uint32_t height, col0, ncols, tile0, x0, tile1, tile2; };   // q: the table's first column in the dense buffer; x0: its dense index; tile0/1/2: first tile in the round-0 / one-level / two-level fold launches
 constexpr uint32_t JG_TAB_PAIRS = 256;                                       // row pairs per tile
 constexpr uint32_t JG_COL_SLICE = 64;                                        // columns per table descriptor (see where the tables are listed)
+static_assert(JG_COL_SLICE <= 0x3fffu, "jg_round01_tables accumulates a descriptor's columns in one kb::DotAcc window");
 __global__ __launch_bounds__(256) void jg_round0_tables(const JgTab* __restrict__ tabs, uint32_t n_tabs, uint32_t n_tiles,
                                                         JgJ J, JgTail tail) {
     Ext e0 = kb::ext_zero(), eh = kb::ext_zero();
@@ -222,20 +223,25 @@ __global__ __launch_bounds__(256) void jg_round01_tables(const JgTab* __restrict
         kb::DotAcc u[4];
 #pragma unroll
         for (int l = 0; l < 4; l++) kb::dot_init(u[l]);
+        // a descriptor is at most JG_COL_SLICE columns (<= 2^16 terms per accumulator); four columns per step, the four 16-byte
+        // loads of a step issued before its first multiply-add
         const uint32_t* col = t.q + 4 * (size_t)k;
-        for (uint32_t c = 0; c < t.ncols; c++, col += t.height) {
-            if ((c & 0x3fffu) == 0x3fffu) {               // 2^14 columns per accumulator window (never in practice)
-                flush(u, k);
-#pragma unroll
-                for (int l = 0; l < 4; l++) kb::dot_init(u[l]);
-            }
-            const uint4 v = *reinterpret_cast<const uint4*>(col);
+        auto add = [&](uint32_t c, const uint4& v) {
             const Ext w = ld_ext(J.col_eq, t.col0 + c);   // wave-uniform
             kb::dot_add(u[0], w, v.x);
             kb::dot_add(u[1], w, v.y);
             kb::dot_add(u[2], w, v.z);
             kb::dot_add(u[3], w, v.w);
+        };
+        uint32_t c = 0;
+        for (; c + 4 <= t.ncols; c += 4, col += 4 * (size_t)t.height) {
+            uint4 v[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) v[i] = *reinterpret_cast<const uint4*>(col + i * (size_t)t.height);
+#pragma unroll
+            for (int i = 0; i < 4; i++) add(c + i, v[i]);
         }
+        for (; c < t.ncols; c++, col += t.height) add(c, *reinterpret_cast<const uint4*>(col));
         flush(u, k);
     }
     jg_finish8(acc, tail);

@@ -742,6 +742,35 @@ int sp1hip_tracegen_riscv_sha_compress(uint32_t* d_table, uint32_t height, const
 int sp1hip_tracegen_riscv_sha_compress_control(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events,
                                                sp1hip_stream_t stream);
 
+/* Device trace generation for the chips of the POSEIDON2 and UINT256_MUL precompile shards, from the executor's event records as they
+ * are (sp1hip_rv64_poseidon2_events: n_events x 26 u64 on the device — [0] clk, [1] ptr, [2 + 2 i] / [3 + 2 i] the previous timestamp
+ * and the word read of word i < 8, [18 + i] the word written; sp1hip_rv64_uint256_events: 31 u64 — [0] clk, [1] x_ptr, [2] y_ptr,
+ * [3 + 2 i] / [4 + 2 i] the previous timestamp and the word read of x word i < 4, [11 + 2 i] / [12 + 2 i] the same of y word i < 4 and,
+ * for 4 <= i < 8, of modulus word i - 4, [27 + i] the x word written). The reference fills both tables on the host
+ * (crates/core/machine/src/syscall/precompiles/poseidon2/air.rs:L107-L290, uint256/air.rs:L118-L290) and has no device filler for
+ * them. Output as above: column-major [width][height] Montgomery words, one row per event.
+ *   sp1hip_tracegen_riscv_poseidon2     Poseidon2, width 348: clk_high, clk_low, the SyscallAddrOperation of ptr, 8 AddrAddOperation
+ *       values, 8 MemoryAccessCols (the words are rewritten in place at clk), the 8 words written as 16-bit limbs, the 16 + 16
+ *       SP1FieldWordRangeChecker bits of the words written and read, the permutation's 179 columns — computed from the sixteen halves
+ *       of the words READ, low half first, each reduced mod p — and is_real. A padding row (row >= n_events) is zero except for its
+ *       permutation columns, which are those of the zero state.
+ *   sp1hip_tracegen_riscv_uint256_mul   Uint256MulMod, width 371: clk_high, clk_low, two SyscallAddrOperation, 4 + 8 AddrAddOperation
+ *       values, 4 + 4 + 4 MemoryAccessColsU8 (x rewritten at clk + 1; y and the modulus read at clk), the IsZero of the modulus' byte
+ *       sum, modulus_is_not_zero, the FieldOpCols of x y = result + carry m' (result[32], carry[32], witness[63]; m' = m, or 2^256 when
+ *       m = 0: a modulus of 33 byte limbs), the FieldLtCols of result < m (zero when m = 0) and is_real. result and carry are computed
+ *       from the words read, by a 512-step division that is correct for every m, odd or even. A padding row is zero except for its 63
+ *       witness columns, which hold the offset 2^14.
+ * Precondition of the Uint256MulMod row, which holds for every event of a reduced x or y: x y / m' < 2^256. An event beyond it neither
+ * faults nor takes longer — the carry columns take the quotient's low 256 bits and the witness wraps — but its row satisfies no
+ * constraint system. The MemoryLocal records of the touched words: sp1hip_precompile_local_records with { 1, 8, 2, 18, 0 } for
+ * POSEIDON2 (26 words; no second pointer) and with { 1, 4, 3, 27, 1 } and { 2, 8, 11, none, 0 } for UINT256_MUL (31 words; arg2_word
+ * 2). Needs n_events <= height. All argument checks come before any launch; a null pointer is accepted only with a zero count /
+ * height; height == 0 succeeds without a launch. The calls enqueue and return: they do not synchronise. */
+int sp1hip_tracegen_riscv_poseidon2_width(void);      /* 348 */
+int sp1hip_tracegen_riscv_uint256_mul_width(void);    /* 371 */
+int sp1hip_tracegen_riscv_poseidon2(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_uint256_mul(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream);
+
 /* The Byte, Range and Program multiplicities of a shard, counted on the device from the tables that send: the receive side of the
  * byte lookup argument, which the reference computes in `generate_dependencies` of its Byte and Range chips
  * (crates/core/machine/src/bytes/trace.rs:L50-L66, range/trace.rs:L54-L95), and the Program chip's count of executed pcs. Generic over

@@ -282,6 +282,10 @@ PROTOTYPES = [
     ("sp1hip_tracegen_riscv_sha_extend_control", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_sha_compress", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_sha_compress_control", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_poseidon2_width", None, []),
+    ("sp1hip_tracegen_riscv_uint256_mul_width", None, []),
+    ("sp1hip_tracegen_riscv_poseidon2", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_uint256_mul", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_lookup_count_sends", None, [u32p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, _vp]),
     ("sp1hip_lookup_count_program", None, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, _vp, _vp, C.c_uint32, _vp]),
     ("sp1hip_lookup_counts_finish", None, [_vp, C.c_uint64, _vp, _vp, _vp]),

@@ -843,6 +843,28 @@ def tracegen_riscv_sha_compress_control(events, height, stream=None):
     return tracegen_riscv_records("ShaCompressControl", events, height, stream)
 
 
+POSEIDON2_EVENT_WORDS, UINT256_EVENT_WORDS = 26, 31                                # SP1HIP_RV64_POSEIDON2_WORDS, _UINT256_WORDS
+# the POSEIDON2 and UINT256_MUL kinds in the shape of PRECOMPILE_DESCRIPTORS — what riscv_more_trace.poseidon2_shard_from /
+# uint256_shard_from hand _close_precompile_shard: POSEIDON2's 8 words rewritten in place at clk; UINT256_MUL's 4 words of x (written at
+# clk + 1), then the 8 words of y and the modulus (read at clk), arg2 = y_ptr
+WORD_DESCRIPTORS = {"poseidon2": (POSEIDON2_EVENT_WORDS, 0x33, -1, ((1, 8, 2, 18, 0),)),
+                    "uint256": (UINT256_EVENT_WORDS, 0x1D, 2, ((1, 4, 3, 27, 1), (2, 8, 11, None, 0)))}
+
+
+def tracegen_riscv_poseidon2(events, height, stream=None):
+    """`generate_trace_device` for the Poseidon2 chip (sp1hip_tracegen_riscv_poseidon2): events = a device int64 tensor [n, 26] of the
+    executor's POSEIDON2 records (riscv_exec.ExecutedShard.poseidon2); one row per event, height >= n; a padding row is zero except for
+    the permutation of the zero state. Returns the column-major [348][height] table as a ColMajor."""
+    return tracegen_riscv_records("Poseidon2", events, height, stream)
+
+
+def tracegen_riscv_uint256_mul(events, height, stream=None):
+    """`generate_trace_device` for the Uint256MulMod chip (sp1hip_tracegen_riscv_uint256_mul): events = a device int64 tensor [n, 31] of
+    the executor's UINT256_MUL records (ExecutedShard.uint256); one row per event, height >= n; a padding row is zero except for the
+    witness offset. Returns the column-major [371][height] table as a ColMajor."""
+    return tracegen_riscv_records("Uint256MulMod", events, height, stream)
+
+
 # chip: (entry point, u64 words of a record, leading chip argument or None) — every chip whose table is made from its record stream
 # alone, the wrappers above by chip name (MemoryLocal, MemoryGlobal*, SyscallCore and SyscallPrecompile also write Global events)
 RISCV_TRACEGEN = {**{c: ("sp1hip_tracegen_riscv_alu", ALU_EVENT_WORDS, k) for c, k in RISCV_ALU_CHIPS.items()},
@@ -858,7 +880,9 @@ RISCV_TRACEGEN = {**{c: ("sp1hip_tracegen_riscv_alu", ALU_EVENT_WORDS, k) for c,
                   "ShaExtend": ("sp1hip_tracegen_riscv_sha_extend", SHA_EXTEND_EVENT_WORDS, None),
                   "ShaExtendControl": ("sp1hip_tracegen_riscv_sha_extend_control", SHA_EXTEND_EVENT_WORDS, None),
                   "ShaCompress": ("sp1hip_tracegen_riscv_sha_compress", SHA_COMPRESS_EVENT_WORDS, None),
-                  "ShaCompressControl": ("sp1hip_tracegen_riscv_sha_compress_control", SHA_COMPRESS_EVENT_WORDS, None)}
+                  "ShaCompressControl": ("sp1hip_tracegen_riscv_sha_compress_control", SHA_COMPRESS_EVENT_WORDS, None),
+                  "Poseidon2": ("sp1hip_tracegen_riscv_poseidon2", POSEIDON2_EVENT_WORDS, None),
+                  "Uint256MulMod": ("sp1hip_tracegen_riscv_uint256_mul", UINT256_EVENT_WORDS, None)}
 
 
 def tracegen_riscv_records(chip, records, height, stream=None):

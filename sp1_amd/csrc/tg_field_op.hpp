@@ -10,7 +10,9 @@
 //   WeierstrassDoubleAssignChip          .../weierstrass/weierstrass_double.rs:L89-L160, L262-L380
 // as sp1_amd/machines/riscv_more_trace.py restates them in Python integers (field_op_columns, _set_field_op, _set_field_lt,
 // _syscall_addr_t, _mem_access_t, _low_bytes, secp256k1_{add,double}_shard_from), which the tests compare every word with. The
-// column offsets are the #[repr(C)] order that riscv_more.weierstrass_add_chip / weierstrass_double_chip transcribe.
+// column offsets are the #[repr(C)] order that riscv_more.weierstrass_add_chip / weierstrass_double_chip transcribe. The
+// multiplication's witness and FieldLtCols also take a modulus that is a row's own data, with one byte limb more than the operands
+// (ModulusTop, field_mul_cols_with, field_lt_cols_of): what tg_uint256_rows.hpp builds Uint256MulMod's row on.
 //
 // A table is column-major [width][height] Montgomery words; one lane (or one host loop iteration) owns one row and stores each
 // value as it is made: a row is never held. Limb, byte and coefficient arrays are indexed by constants only (fully unrolled
@@ -151,47 +153,69 @@ template <int N> TG_HD void field_add_cols(Cursor& w, uint32_t col, uint32_t row
     }
 }
 
-// The same for  a b = r + c p  with c a full 4N-byte quotient: 2 x 4N x 4N byte products. One step per coefficient K, from the top
-// down, as a template recursion: K is a constant in every step, so every byte index is, whatever the compiler's unroll limits.
+// The modulus of a multiplication's witness as byte limbs: the 4N bytes of p, or (ModulusTop) those and one limb more on top, which
+// is 1 for the modulus 2^(32N) — p = 0 — and 0 otherwise (Uint256MulMod, tg_uint256_rows.hpp). byte() takes constants only.
+template <int N> struct ModulusBytes {
+    static constexpr int LIMBS = 4 * N;
+    const uint32_t (&p)[N];
+    TG_HD uint32_t byte(int j) const { return byte_of(p, j); }
+};
+template <int N> struct ModulusTop {
+    static constexpr int LIMBS = 4 * N + 1;
+    const U<N>& p;
+    uint32_t top;
+    TG_HD uint32_t byte(int j) const { return j < 4 * N ? byte_of(p, j) : top; }
+};
+
+// The same for  a b = r + c p  with c a full 4N-byte quotient and p of M::LIMBS byte limbs (4N, or 4N + 1 with ModulusTop): 4N x 4N
+// plus 4N x M::LIMBS byte products, 4N + M::LIMBS - 2 witness columns. One step per coefficient K, from the top down, as a template
+// recursion: K is a constant in every step, so every byte index is, whatever the compiler's unroll limits.
 // The signed coefficients (below 2^23 in magnitude while a b = r + c p holds) are kept in two's complement in uint32_t: an event
 // with unreduced operands, for which the identity fails and the running value grows without bound, wraps instead of overflowing
 // a signed integer, on the host as on the device.
-template <int N, int K> TG_HD void field_mul_witness(Cursor& w, uint32_t acc, const uint32_t (&pa)[4 * N], const uint32_t (&pb)[4 * N],
-                                                     const uint32_t (&pc)[4 * N], const U<N>& r, const Modulus<N>& m, uint32_t offset) {
+template <int N, int K, class M> TG_HD void field_mul_witness(Cursor& w, uint32_t acc, const uint32_t (&pa)[4 * N], const uint32_t (&pb)[4 * N],
+                                                              const uint32_t (&pc)[4 * N], const U<N>& r, const M& m, uint32_t offset) {
     if constexpr (K >= 1) {
-        constexpr int L = 4 * N, LO = K < L ? 0 : K - L + 1, HI = K < L ? K : L - 1;
+        constexpr int L = 4 * N, ML = M::LIMBS, LO = K < L ? 0 : K - L + 1, HI = K < L ? K : L - 1, MLO = K < ML ? 0 : K - ML + 1;
         uint32_t van = 0;
         if constexpr (K < L) van = 0u - byte_of(r, K);
 #pragma unroll
-        for (int i = LO; i <= HI; i++) van += pa[i] * pb[K - i] - pc[i] * byte_of(m.p, K - i);
+        for (int i = LO; i <= HI; i++) van += pa[i] * pb[K - i];
+#pragma unroll
+        for (int i = MLO; i <= HI; i++) van -= pc[i] * m.byte(K - i);
         acc = van + 256u * acc;                                                                  // witness[K - 1] = van[K] + 256 witness[K]
         w.val(acc + offset);
         w.back();
         field_mul_witness<N, K - 1>(w, acc, pa, pb, pc, r, m, offset);
     }
 }
-template <int N> TG_HD void field_mul_cols(Cursor& w, uint32_t col, uint32_t row, const U<N>& shown, const U<N>& a, const U<N>& b, const U<N>& r,
-                                           const U<N>& c, const Modulus<N>& m, uint32_t offset) {
-    constexpr int L = 4 * N;
+template <int N, class M> TG_HD void field_mul_cols_with(Cursor& w, uint32_t col, uint32_t row, const U<N>& shown, const U<N>& a, const U<N>& b,
+                                                         const U<N>& r, const U<N>& c, const M& m, uint32_t offset) {
+    constexpr int L = 4 * N, WITNESS = L + M::LIMBS - 2;
     w.seek(col, row);
     put_bytes(w, shown);
     put_bytes(w, c);
     uint32_t pa[L], pb[L], pc[L];
 #pragma unroll
     for (int i = 0; i < L; i++) pa[i] = byte_of(a, i), pb[i] = byte_of(b, i), pc[i] = byte_of(c, i);
-    w.seek(col + FieldOp<N>::WITNESS_AT + FieldOp<N>::WITNESS - 1, row);
-    field_mul_witness<N, 2 * L - 2>(w, 0, pa, pb, pc, r, m, offset);
+    w.seek(col + 2 * L + WITNESS - 1, row);
+    field_mul_witness<N, WITNESS>(w, 0, pa, pb, pc, r, m, offset);
+}
+template <int N> TG_HD void field_mul_cols(Cursor& w, uint32_t col, uint32_t row, const U<N>& shown, const U<N>& a, const U<N>& b, const U<N>& r,
+                                           const U<N>& c, const Modulus<N>& m, uint32_t offset) {
+    field_mul_cols_with<N>(w, col, row, shown, a, b, r, c, ModulusBytes<N>{m.p}, offset);
 }
 
-// FieldLtCols for lhs < the modulus: the flag at the most significant byte where they differ, and the two bytes there.
-template <int N> TG_HD void field_lt_cols(Cursor& w, uint32_t col, uint32_t row, const U<N>& lhs, const Modulus<N>& m) {
+// FieldLtCols for lhs < rhs (U<N>, or the limbs of a modulus): the flag at the most significant byte where they differ, and the
+// two bytes there.
+template <int N, class R> TG_HD void field_lt_cols_of(Cursor& w, uint32_t col, uint32_t row, const U<N>& lhs, const R& rhs) {
     constexpr int L = 4 * N;
     int at = L - 1;
-    uint32_t lb = byte_of(lhs, L - 1), rb = byte_of(m.p, L - 1);
+    uint32_t lb = byte_of(lhs, L - 1), rb = byte_of(rhs, L - 1);
     bool found = false;
 #pragma unroll
     for (int i = L - 1; i >= 0; i--) {
-        const uint32_t x = byte_of(lhs, i), y = byte_of(m.p, i);
+        const uint32_t x = byte_of(lhs, i), y = byte_of(rhs, i);
         const bool hit = !found && x != y;
         at = hit ? i : at;
         lb = hit ? x : lb;
@@ -202,6 +226,9 @@ template <int N> TG_HD void field_lt_cols(Cursor& w, uint32_t col, uint32_t row,
     for (int i = 0; i < L; i++) w.bit(i == at);
     w.val(lb);
     w.val(rb);
+}
+template <int N> TG_HD void field_lt_cols(Cursor& w, uint32_t col, uint32_t row, const U<N>& lhs, const Modulus<N>& m) {
+    field_lt_cols_of<N>(w, col, row, lhs, m.p);
 }
 
 // The field operations of a row: each computes its result from reduced operands and writes its FieldOpCols at `col`.

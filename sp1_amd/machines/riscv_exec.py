@@ -660,19 +660,29 @@ def device_memory_shard(init_addrs, init_recs, fin_addrs, fin_recs, prep, ctx, p
 
 DEVICE_PRECOMPILE_KINDS = ("keccak", "secp256k1_add", "secp256k1_double")
 DEVICE_SHA_KINDS = ("sha_extend", "sha_compress")             # their descriptors are api.SHA_DESCRIPTORS
+DEVICE_WORD_KINDS = ("poseidon2", "uint256")                  # their descriptors are api.WORD_DESCRIPTORS
+
+
+def _precompile_descriptor(kind):
+    """(event words, syscall id, arg2 word, MemoryLocal segments) of a device-made precompile kind, from the table that has it."""
+    from .. import api
+    for table in (api.PRECOMPILE_DESCRIPTORS, api.SHA_DESCRIPTORS, api.WORD_DESCRIPTORS):
+        if kind in table:
+            return table[kind]
+    raise KeyError("no device descriptor for a %r shard" % (kind,))
 
 
 def device_precompile_shard(kind, events, prep, ctx, stream=None):
-    """A provable precompile shard of `kind` (DEVICE_PRECOMPILE_KINDS, DEVICE_SHA_KINDS) from the executor's event records alone ([n, 77 /
-    43 / 26 / 786 / 155] int64, numpy or torch), every table made ON THE DEVICE: (machine, chips, publics, global events) in the shape
+    """A provable precompile shard of `kind` (DEVICE_PRECOMPILE_KINDS, DEVICE_SHA_KINDS, DEVICE_WORD_KINDS) from the executor's event records
+    alone ([n, 77 / 43 / 26 / 786 / 155 / 26 / 31] int64, numpy or torch), every table made ON THE DEVICE: (machine, chips, publics, global events) in the shape
     of device_core_shard. The wide tables come from api.tracegen_riscv_keccak / _keccak_control / _secp256k1_add / _double /
-    _sha_extend / _sha_extend_control / _sha_compress / _sha_compress_control; SyscallPrecompile
+    _sha_extend / _sha_extend_control / _sha_compress / _sha_compress_control / _poseidon2 / _uint256_mul; SyscallPrecompile
     (api.tracegen_riscv_syscall_precompile) and the MemoryLocal records of the touched words (api.precompile_local_records, one
-    record per word of each call) from the same records by api.PRECOMPILE_DESCRIPTORS[kind] or api.SHA_DESCRIPTORS[kind]; MemoryLocal and Global as in a core
+    record per word of each call) from the same records by api.PRECOMPILE_DESCRIPTORS[kind], api.SHA_DESCRIPTORS[kind] or api.WORD_DESCRIPTORS[kind]; MemoryLocal and Global as in a core
     shard — MemoryLocal's two events per record first, then SyscallPrecompile's receives —; the public values are the program's
     initial state with the Global fields set. No Tracer, no host table."""
     from .. import api
-    words, syscall_id, arg2_word, segments = (api.SHA_DESCRIPTORS if kind in DEVICE_SHA_KINDS else api.PRECOMPILE_DESCRIPTORS)[kind]
+    words, syscall_id, arg2_word, segments = _precompile_descriptor(kind)
     chip, control, rows_per_call, _ = PRECOMPILES[kind]
     with torch.cuda.stream(stream or torch.cuda.current_stream()):
         ev = _on_device(events, words)
@@ -690,19 +700,20 @@ def device_precompile_shard(kind, events, prep, ctx, stream=None):
 
 
 DEVICE_KINDS = ("core", "memory") + DEVICE_PRECOMPILE_KINDS + DEVICE_SHA_KINDS
+DEVICE_SHARD_KINDS = DEVICE_KINDS + DEVICE_WORD_KINDS        # every kind the executor records
 
 
 def device_shard(executor, rec, prep, stream=None):
-    """One shard of a run (`rec`: a ShardRecords of run_records, its kind one of DEVICE_KINDS) made ON THE DEVICE by the builder of
+    """One shard of a run (`rec`: a ShardRecords of run_records, its kind one of DEVICE_SHARD_KINDS) made ON THE DEVICE by the builder of
     its kind — device_core_shard, device_memory_shard or device_precompile_shard: (machine, chips, publics, global events [count, 9])."""
     if rec.kind == "core":
         return device_core_shard(executor, rec.executed, prep, prev=rec.prev, stream=stream)
     if rec.kind == "memory":
         return device_memory_shard(rec.init_addrs, rec.init_recs, rec.fin_addrs, rec.fin_recs, prep, rec.ctx, previous_init=rec.previous_init,
                                    previous_fin=rec.previous_fin, stream=stream)
-    if rec.kind in DEVICE_PRECOMPILE_KINDS or rec.kind in DEVICE_SHA_KINDS:
+    if rec.kind in DEVICE_SHARD_KINDS:
         return device_precompile_shard(rec.kind, rec.events, prep, rec.ctx, stream=stream)
-    raise ValueError("no device builder for a %r shard: device_shard makes %s" % (rec.kind, ", ".join(DEVICE_KINDS)))
+    raise ValueError("no device builder for a %r shard: device_shard makes %s" % (rec.kind, ", ".join(DEVICE_SHARD_KINDS)))
 
 
 def execution_public_values(sh, prev=None):

@@ -64,10 +64,27 @@ def _gpu_prove(api, monkeypatch, env, chips, zc, L, seed, zeta, alpha, gkr, publ
         ch.observe(orc.random_felts((8,), seed))
         assert np.array_equal(ch.sample_point(L), zeta)
         assert np.array_equal(ch.sample_ext_element(), alpha) and np.array_equal(ch.sample_ext_element(), gkr)
-        dev = [api.ZerocheckChip(air, api.ColMajor.from_row_major_host(main), api.ColMajor.from_row_major_host(prep) if prep is not None else None)
-               for _, air, main, prep in chips]
+        # (a chip without rows has no tables: tests/test_gpu_zc_real.py)
+        up = lambda t: api.ColMajor.from_row_major_host(t) if t is not None and t.shape[0] else None
+        dev = [api.ZerocheckChip(air, up(main), up(prep)) for _, air, main, prep in chips]
         blob = api.zerocheck(dev, L, zeta, np.concatenate([c.openings for c in zc]), alpha, gkr, publics, ch)
         return blob, ch.state()
+
+
+def three_proofs(api, monkeypatch, tables, L, seed, env):
+    """tables: [(label, air, main, prep)]. The same tables proved by the oracle (its `two_round_form` on the default path), by the
+    pieces and by the interpreter (SP1HIP_ZC_MACRO=0): ((bytes, final transcript state) of each, in that order), and what a
+    failure message says about them, or None where all bytes are equal."""
+    chips, zc, zeta, alpha, gkr, publics, o_ch = setup(tables, L, seed)
+    two_rounds = L >= 2 and env.get("SP1HIP_ZC_BIVARIATE") != "0"
+    want = orc.zerocheck_prove(zc, L, zeta, alpha, gkr, publics, o_ch, two_round_form=two_rounds)
+    pieces, p_state = _gpu_prove(api, monkeypatch, env, chips, zc, L, seed, zeta, alpha, gkr, publics)
+    interp, i_state = _gpu_prove(api, monkeypatch, dict(env, SP1HIP_ZC_MACRO="0"), chips, zc, L, seed, zeta, alpha, gkr, publics)
+    differ = None
+    if not (pieces == want and interp == want):
+        differ = ("pieces vs oracle: %s | interpreter vs oracle: %s | pieces vs interpreter: %s"
+                  % (_first_difference(pieces, want, L), _first_difference(interp, want, L), _first_difference(pieces, interp, L)))
+    return ((want, o_ch.state()), (pieces, p_state), (interp, i_state)), differ
 
 
 def check(api, monkeypatch, spec, L, source, seed, env=None, mul_min_rows="1"):
@@ -77,16 +94,11 @@ def check(api, monkeypatch, spec, L, source, seed, env=None, mul_min_rows="1"):
         env["SP1HIP_ZC_MUL_MIN_ROWS"] = mul_min_rows
     src = _source(source, seed)
     tables = [(label,) + arbitrary_chip(chip, rows, src) for label, chip, rows in spec]
-    chips, zc, zeta, alpha, gkr, publics, o_ch = setup(tables, L, seed)
-    two_rounds = L >= 2 and env.get("SP1HIP_ZC_BIVARIATE") != "0"
-    want = orc.zerocheck_prove(zc, L, zeta, alpha, gkr, publics, o_ch, two_round_form=two_rounds)
-    pieces, p_state = _gpu_prove(api, monkeypatch, env, chips, zc, L, seed, zeta, alpha, gkr, publics)
-    interp, i_state = _gpu_prove(api, monkeypatch, dict(env, SP1HIP_ZC_MACRO="0"), chips, zc, L, seed, zeta, alpha, gkr, publics)
-    if not (pieces == want and interp == want):
-        pytest.fail("%s, L = %d, %s: pieces vs oracle: %s | interpreter vs oracle: %s | pieces vs interpreter: %s"
-                    % (spec, L, source, _first_difference(pieces, want, L), _first_difference(interp, want, L), _first_difference(pieces, interp, L)))
-    assert np.array_equal(p_state, o_ch.state()), "pieces: transcript state"
-    assert np.array_equal(i_state, o_ch.state()), "interpreter: transcript state"
+    ((_, o_state), (_, p_state), (_, i_state)), differ = three_proofs(api, monkeypatch, tables, L, seed, env)
+    if differ:
+        pytest.fail("%s, L = %d, %s: %s" % (spec, L, source, differ))
+    assert np.array_equal(p_state, o_state), "pieces: transcript state"
+    assert np.array_equal(i_state, o_state), "interpreter: transcript state"
 
 
 # ---- small heights: a missing last row of a pair (has1 false: 1, 3, 5, 7), quads with 1, 2 and 3 live rows (1 | 5, 2 | 6, 3 | 7),

@@ -97,6 +97,8 @@ def program_run(api, program="fibonacci", cycles=26_000_000, L=22, lsh=21):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--program", default="rsp")
+    ap.add_argument("--elf", default="", help="prove this ELF file, run without input, instead of a bundled guest (a hand-assembled test program: "
+                    "tests/field_chip_cases.py::mixed_program calls a curve's and a tower field's precompiles, which no bundled guest does)")
     ap.add_argument("--cycles", type=int, default=0, help="size the input for at least this many cycles (not for rsp: its input is a recorded block)")
     ap.add_argument("--shard-cycles", type=int, default=0, help="cut core shards at this many cycles instead of by trace area (the default: the "
                     "reference's rule, ShapeChecker with ELEMENT_THRESHOLD 2^28 + 2^27 / HEIGHT_THRESHOLD 2^22, inside the executor)")
@@ -106,12 +108,12 @@ def main():
     ap.add_argument("--in-flight", type=int, default=0, help="after the shard-by-shard pass, prove ALL shards again through the library's "
                     "prover pool with this many proofs in flight (tables resident in HBM; proofs must equal the first pass's)")
     ap.add_argument("--only-kinds", default="", help="comma-separated shard kinds: build every shard, prove only these (a profile of one kind)")
-    ap.add_argument("--device-shard", action="store_true", help="core, memory and precompile shards (riscv_exec.DEVICE_SHARD_KINDS): make the WHOLE shard on the device "
-                    "from the executor's records (riscv_exec.device_shard over run_records — device_core_shard: the event partition kernel, every chip's table, the public "
+    ap.add_argument("--device-shard", action="store_true", help="core, memory and precompile shards (riscv_exec.DEVICE_SHARD_KINDS + DEVICE_FAMILY_KINDS): make the WHOLE shard on the device "
+                    "from the executor's records (riscv_exec.device_shard_of over run_records — device_core_shard: the event partition kernel, every chip's table, the public "
                     "values' Global fields, the lookup counts; device_memory_shard: MemoryGlobalInit / Finalize from the run's address lists; "
-                    "device_precompile_shard: the wide tables, SyscallPrecompile, MemoryLocal from the calls' event records) — no tracer and "
+                    "device_precompile_shard / device_family_shard: the wide tables, SyscallPrecompile, MemoryLocal from the calls' event records) — no tracer and "
                     "no host table is built for them; the public values are chained by the previous shard's, the Global events still join "
-                    "the run's balance check. The fifteen family kinds of precompile keep the host "
+                    "the run's balance check. ed_add, ed_decompress and uint256_ops keep the host "
                     "path. MemoryBump's rows stand in another order than the host tracer's, so a core shard that crosses 2^24 cycles proves "
                     "to other bytes (the same statement)")
     ap.add_argument("--verify", action="store_true")
@@ -134,7 +136,11 @@ def main():
         api.check(lib.sp1hip_timers_enable(1))
     shard_cycles = args.shard_cycles or 1 << 40
     L, lsh = 22, 21
-    ex = X.Executor(X.guest_file(args.program + ".elf"), stdin=stdin_of(args.program, args.cycles or 3 * FULL_CYCLES_OF[args.program]))
+    if args.elf:
+        with open(args.elf, "rb") as f:
+            ex, args.program = X.Executor(f.read(), stdin=[]), os.path.basename(args.elf)
+    else:
+        ex = X.Executor(X.guest_file(args.program + ".elf"), stdin=stdin_of(args.program, args.cycles or 3 * FULL_CYCLES_OF[args.program]))
     if not args.shard_cycles:
         ex.cut_by_area()
     shards, gevs, kept, cycles, last, resident, pvs, pk, pk_prep, warmed = [], [], {}, 0, None, [], [], None, None, {}
@@ -142,10 +148,10 @@ def main():
     t_prev = t_all
     for rec in X.run_records(ex, shard_cycles, core_limit=args.core_shards or None):
         kind, sh, tabs, device_chips = rec.kind, rec.executed, None, None
-        if args.device_shard and kind in X.DEVICE_SHARD_KINDS:                # no tracer and no host table for these
+        if args.device_shard and kind in X.DEVICE_SHARD_KINDS + X.DEVICE_FAMILY_KINDS:                # no tracer and no host table for these
             if pk_prep is None:
                 pk_prep = {n: to_col_major(t) for n, t in X.preprocessed_tables(ex, "cuda").items()}
-            machine, device_chips, publics, gev9 = X.device_shard(ex, rec, pk_prep)
+            machine, device_chips, publics, gev9 = X.device_shard_of(ex, rec, pk_prep)
             gev = X.global_events_11(gev9)
         else:
             machine, tabs, publics, gev = X.host_shard(ex, rec, device)

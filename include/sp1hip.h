@@ -659,6 +659,11 @@ int sp1hip_tracegen_riscv_memory_global(int finalize, uint32_t* d_table, uint32_
                                         uint64_t previous_addr, int32_t* d_global_events, sp1hip_stream_t stream);
 int sp1hip_tracegen_riscv_syscall_precompile(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, uint32_t words_per_event,
                                              uint32_t syscall_id, int32_t arg2_word, int32_t* d_global_events, sp1hip_stream_t stream);
+/* The same for a shard that mixes system calls (FpOpAssign, Fp2AddSubAssign): each row's syscall id is the low byte of its own event
+ * word code_word (code_word < words_per_event) instead of one id per call. */
+int sp1hip_tracegen_riscv_syscall_precompile_coded(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events,
+                                                   uint32_t words_per_event, uint32_t code_word, int32_t arg2_word, int32_t* d_global_events,
+                                                   sp1hip_stream_t stream);
 int sp1hip_precompile_local_records(uint64_t* d_records, uint64_t records_capacity, const uint64_t* d_events, uint32_t n_events, uint32_t words_per_event,
                                     const uint32_t* segments, uint32_t n_segments, sp1hip_stream_t stream);
 
@@ -704,6 +709,31 @@ int sp1hip_tracegen_riscv_secp256k1_double_width(void);   /* 1591 */
 int sp1hip_tracegen_riscv_secp256k1_add(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream);
 int sp1hip_tracegen_riscv_secp256k1_double(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events,
                                            sp1hip_stream_t stream);
+
+/* Device trace generation for the Weierstrass and Fp / Fp2 precompile chips of SP1HIP_RV64_FAMILY_* 0..11 (below), from the executor's
+ * event records as sp1hip_rv64_precompile_events gives them (n_events x words u64 on the device): [0] clk, [1] arg1, [2] arg2, [3] the
+ * system-call code — a FOUR-word head —, then per word i < W of the first operand [4 + 2i] / [5 + 2i] the previous timestamp and the
+ * word read, the same of the second operand at [4 + 2W + 2i] (additions and the tower chips), then the W words written.
+ *   family 0..5   Secp256r1 / Bn254 / Bls12381 AddAssign, DoubleAssign   W = 8, 8, 12    width 1599 / 1591, 1599 / 1591, 2399 / 2391
+ *   family 6, 7   Bn254 / Bls12381 FpOpAssign                           W = 4, 6        width 306, 450
+ *   family 8, 9   Bn254 / Bls12381 Fp2AddSubAssign                      W = 8, 12       width 592, 880
+ *   family 10, 11 Bn254 / Bls12381 Fp2MulAssign                         W = 8, 12       width 1095, 1639
+ * The reference fills these tables on the host (crates/core/machine/src/syscall/precompiles/weierstrass, fptower) and has no device
+ * filler for them. Output: column-major [width][height] Montgomery words, one row per event. An FpOpAssign / Fp2AddSubAssign row takes
+ * its operation from the low byte of word 3, so one call may mix ADD, SUB (and MUL). A padding row is the reference's dummy row: an
+ * addition's field operations on p = (0, 0), q = (1, 1) with the dummy access record in q_access[0] and q_access[W / 2]; a doubling's on
+ * p = (0, 1) with the record in p_access[W / 2]; a tower chip's operation on zero operands as an addition (is_add = 1).
+ * The table is made in two launches through a work buffer of ops x (3 N + 1) x height u32 (N = 8 or 12 limbs of a field element;
+ * ops = 10 / 11 / 1 / 2 / 6 FieldOpCols per row), which the call allocates and releases itself in stream order (hipMallocAsync /
+ * hipFreeAsync on `stream`): the caller passes no scratch. Operands must be reduced, q.x != p.x for an addition, p.y != 0 for a
+ * doubling, which the executor guarantees; an event that breaks it neither faults nor spins but its row satisfies no constraint
+ * system. Families 12..14 (EdAddAssign, EdDecompress, Uint256Ops) and anything larger are refused with
+ * SP1HIP_ERROR_INVALID_ARGUMENT and a message that names the family; the width query returns -1 for them. The other argument checks
+ * are those above: n_events <= height, a null pointer only with a zero count / height, height == 0 succeeds without a launch. The
+ * call enqueues and returns: it does not synchronise. */
+int sp1hip_tracegen_riscv_field_chip_width(uint32_t family);   /* -1: no device filler */
+int sp1hip_tracegen_riscv_field_chip(uint32_t family, uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events,
+                                     sp1hip_stream_t stream);
 
 /* Device trace generation for the four chips of the SHA_EXTEND and SHA_COMPRESS precompile shards, from the executor's event records
  * as they are (sp1hip_rv64_sha_extend_events: n_events x 786 u64 on the device — [0] clk, [1] w_ptr, [2 + 11 r ..] step r < 48: four

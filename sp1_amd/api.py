@@ -865,6 +865,49 @@ def tracegen_riscv_uint256_mul(events, height, stream=None):
     return tracegen_riscv_records("Uint256MulMod", events, height, stream)
 
 
+FAMILY_CODE_WORD = 3                                                               # the system-call code's word of a family event
+# kind: (SP1HIP_RV64_FAMILY_*, u64 words per operand, operands, syscall id or None) — the twelve field / curve precompile kinds of
+# riscv_exec.FAMILIES with a device filler (sp1hip_tracegen_riscv_field_chip). None: the shard mixes system calls (Fp: ADD, SUB, MUL;
+# Fp2: ADD, SUB) and each row's id is its event's own (tracegen_riscv_syscall_precompile_coded, word FAMILY_CODE_WORD)
+FIELD_CHIP_KINDS = {"secp256r1_add": (0, 8, 2, 0x2C), "secp256r1_double": (1, 8, 1, 0x2D), "bn254_add": (2, 8, 2, 0x0E), "bn254_double": (3, 8, 1, 0x0F),
+                    "bls12381_add": (4, 12, 2, 0x1E), "bls12381_double": (5, 12, 1, 0x1F), "bn254_fp": (6, 4, 2, None), "bls12381_fp": (7, 6, 2, None),
+                    "bn254_fp2_addsub": (8, 8, 2, None), "bls12381_fp2_addsub": (9, 12, 2, None), "bn254_fp2_mul": (10, 8, 2, 0x2B),
+                    "bls12381_fp2_mul": (11, 12, 2, 0x25)}
+
+
+def _family_descriptor(nw, operands, syscall_id):
+    """A family event is clk, arg1, arg2, code, `nw` (previous timestamp, word) pairs per operand, `nw` words written: two operands
+    — x rewritten at clk + 1, y read at clk, arg2 = y's pointer — or one, rewritten in place at clk."""
+    if operands == 2:
+        return (4 + 5 * nw, syscall_id, 2, ((1, nw, 4, 4 + 4 * nw, 1), (2, nw, 4 + 2 * nw, None, 0)))
+    return (4 + 3 * nw, syscall_id, -1, ((1, nw, 4, 4 + 2 * nw, 0),))
+
+
+# the same kinds in the shape of PRECOMPILE_DESCRIPTORS — what riscv_more_trace.family_shard_from hands _close_precompile_shard
+FAMILY_DESCRIPTORS = {kind: _family_descriptor(nw, operands, syscall_id) for kind, (_, nw, operands, syscall_id) in FIELD_CHIP_KINDS.items()}
+
+
+def tracegen_riscv_field_chip(kind, events, height, stream=None):
+    """`generate_trace_device` for the chip of a field / curve precompile kind of FIELD_CHIP_KINDS (sp1hip_tracegen_riscv_field_chip):
+    events = a device int64 tensor [n, FAMILY_DESCRIPTORS[kind][0]] of the executor's records of that family
+    (riscv_exec.ExecutedShard.precompile_events); one row per event, height >= n, padding rows = the reference's dummy row. The
+    call's work buffer is allocated and released inside it, on the stream. Returns the column-major [width][height] table as a ColMajor."""
+    if kind not in FIELD_CHIP_KINDS:
+        raise ValueError("no device filler for a %r chip: tracegen_riscv_field_chip makes %s" % (kind, ", ".join(FIELD_CHIP_KINDS)))
+    return _tracegen_records("sp1hip_tracegen_riscv_field_chip", FAMILY_DESCRIPTORS[kind][0], FIELD_CHIP_KINDS[kind][0], events, height, stream)
+
+
+def tracegen_riscv_syscall_precompile_coded(events, height, code_word=FAMILY_CODE_WORD, arg2_word=-1, global_events=None, stream=None):
+    """tracegen_riscv_syscall_precompile for a shard that mixes system calls (sp1hip_tracegen_riscv_syscall_precompile_coded): each
+    row's syscall id is the low byte of its event's word `code_word`."""
+    n = _n_records(events)
+    d_global_events = _global_events_ptr(global_events, n)
+    out = device_words(SYSCALL_PRECOMPILE_WIDTH * int(height))
+    check(_L().sp1hip_tracegen_riscv_syscall_precompile_coded(_dptr(out), int(height), _dptr(events) if n else None, n, int(events.shape[1]), int(code_word),
+                                                              int(arg2_word), d_global_events, _stream_ptr(stream)))
+    return ColMajor(out, int(height), SYSCALL_PRECOMPILE_WIDTH)
+
+
 # chip: (entry point, u64 words of a record, leading chip argument or None) — every chip whose table is made from its record stream
 # alone, the wrappers above by chip name (MemoryLocal, MemoryGlobal*, SyscallCore and SyscallPrecompile also write Global events)
 RISCV_TRACEGEN = {**{c: ("sp1hip_tracegen_riscv_alu", ALU_EVENT_WORDS, k) for c, k in RISCV_ALU_CHIPS.items()},

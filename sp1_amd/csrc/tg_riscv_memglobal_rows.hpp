@@ -124,6 +124,21 @@ struct SyscallPrecompile : ZeroPaddedChip<SYSCALL_PRECOMPILE_WIDTH, uint64_t> {
         }
     }
 };
+// The same for a shard that mixes system calls (FpOpAssign: ADD, SUB, MUL; Fp2AddSubAssign: ADD, SUB): the id is the low byte of
+// the event's own word `code_word`
+struct SyscallPrecompileCoded : ZeroPaddedChip<SYSCALL_PRECOMPILE_WIDTH, uint64_t> {
+    static TG_HD void live(Row<WIDTH>& r, const uint64_t* __restrict__ events, uint32_t row, uint32_t words_per_event, uint32_t code_word, int arg2_word,
+                           int32_t* __restrict__ global_events) {
+        const uint64_t* e = events + (size_t)row * words_per_event;
+        const uint32_t syscall_id = (uint32_t)e[code_word] & 0xffu;
+        fill_syscall_precompile(r, e, syscall_id, arg2_word);
+        if (global_events) {
+            int32_t ev[GLOBAL_EVENT_WORDS];
+            syscall_precompile_global_event(ev, e, syscall_id, arg2_word);
+            store_global_events<1>(global_events, row, ev);
+        }
+    }
+};
 
 // One run of consecutive words a precompile touches through one pointer: event word ptr_word holds the pointer, `count` words
 // follow it in memory; event words pairs_word + 2 i, + 2 i + 1 hold word i's previous timestamp and value, event word final_word + i

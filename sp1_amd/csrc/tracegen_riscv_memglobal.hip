@@ -53,6 +53,14 @@ int sp1hip_tracegen_riscv_syscall_precompile(uint32_t* d_table, uint32_t height,
                            words_per_event, syscall_id, arg2_word, d_global_events);
 }
 
+int sp1hip_tracegen_riscv_syscall_precompile_coded(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, uint32_t words_per_event,
+                                                   uint32_t code_word, int32_t arg2_word, int32_t* d_global_events, sp1hip_stream_t stream) {
+    SP1HIP_REQUIRE(words_per_event >= 2 && words_per_event <= 65536 && code_word < words_per_event && arg2_word >= -1 && arg2_word < (int32_t)words_per_event,
+                   "bad event shape: need 2 <= words_per_event <= 65536, code_word < words_per_event, -1 <= arg2_word < words_per_event");
+    return tg::launch_rows(__func__, tg::row_kernel<tg::SyscallPrecompileCoded, uint32_t, uint32_t, int, int32_t*>, d_table, height, d_events, n_events, stream,
+                           words_per_event, code_word, arg2_word, d_global_events);
+}
+
 int sp1hip_precompile_local_records(uint64_t* d_records, uint64_t records_capacity, const uint64_t* d_events, uint32_t n_events, uint32_t words_per_event,
                                     const uint32_t* segments, uint32_t n_segments, sp1hip_stream_t stream) {
     SP1HIP_REQUIRE(segments && n_segments >= 1 && n_segments <= (uint32_t)tg::PRECOMPILE_MAX_SEGMENTS, "need 1 to 4 segments");

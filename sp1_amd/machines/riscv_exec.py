@@ -684,16 +684,33 @@ def device_precompile_shard(kind, events, prep, ctx, stream=None):
     from .. import api
     words, syscall_id, arg2_word, segments = _precompile_descriptor(kind)
     chip, control, rows_per_call, _ = PRECOMPILES[kind]
+
+    def wide(ev, n):
+        made = {chip: api.tracegen_riscv_records(chip, ev, RT.pad32(rows_per_call * n), stream=stream)}
+        if control:
+            made[control] = api.tracegen_riscv_records(control, ev, RT.pad32(n), stream=stream)
+        return made
+    return _device_precompile_shard(events, words, wide, syscall_id, arg2_word, segments, prep, ctx, stream)
+
+
+def _device_precompile_shard(events, words, wide, syscall_id, arg2_word, segments, prep, ctx, stream):
+    """The body device_precompile_shard and device_family_shard share: the events uploaded as they are, the kind's wide tables
+    (wide(events, n) -> {chip: ColMajor}), SyscallPrecompile into the tail of MemoryLocal's Global events — one `syscall_id` for all
+    rows, or None for each event's own code (api.tracegen_riscv_syscall_precompile_coded) —, MemoryLocal from the touched words'
+    records, Global, the public values, the counted tables."""
+    from .. import api
     with torch.cuda.stream(stream or torch.cuda.current_stream()):
         ev = _on_device(events, words)
         n = int(ev.shape[0])
         assert n, "a precompile shard has at least one call"
-        made = {chip: api.tracegen_riscv_records(chip, ev, RT.pad32(rows_per_call * n), stream=stream)}
-        if control:
-            made[control] = api.tracegen_riscv_records(control, ev, RT.pad32(n), stream=stream)
+        made = wide(ev, n)
+        if syscall_id is None:
+            syscalls = lambda tail: api.tracegen_riscv_syscall_precompile_coded(ev, RT.pad32(n), api.FAMILY_CODE_WORD, arg2_word, global_events=tail, stream=stream)
+        else:
+            syscalls = lambda tail: api.tracegen_riscv_syscall_precompile(ev, RT.pad32(n), syscall_id, arg2_word, global_events=tail, stream=stream)
         pv = PVM.no_memory_events(PVM.initialized_state(ctx.pc_start))
-        gev, _, _ = _local_and_global_tables(made, api.precompile_local_records(ev, segments, stream=stream), n, stream, pv=pv, fill=lambda tail: made.update(
-            SyscallPrecompile=api.tracegen_riscv_syscall_precompile(ev, RT.pad32(n), syscall_id, arg2_word, global_events=tail, stream=stream)))
+        gev, _, _ = _local_and_global_tables(made, api.precompile_local_records(ev, segments, stream=stream), n, stream, pv=pv,
+                                             fill=lambda tail: made.update(SyscallPrecompile=syscalls(tail)))
         publics = PVM.to_tensor(pv)
         machine, chips = _close_device_shard(made, prep, RT.smallest_cluster(set(made) | set(prep)), publics, ctx, stream)
         return machine, chips, publics, gev
@@ -714,6 +731,32 @@ def device_shard(executor, rec, prep, stream=None):
     if rec.kind in DEVICE_SHARD_KINDS:
         return device_precompile_shard(rec.kind, rec.events, prep, rec.ctx, stream=stream)
     raise ValueError("no device builder for a %r shard: device_shard makes %s" % (rec.kind, ", ".join(DEVICE_SHARD_KINDS)))
+
+
+DEVICE_FAMILY_KINDS = tuple(FAMILIES)[:12]                   # the curve and Fp / Fp2 kinds; their descriptors are api.FAMILY_DESCRIPTORS
+
+
+def device_family_shard(kind, events, prep, ctx, stream=None):
+    """A provable precompile shard of a field / curve `kind` (DEVICE_FAMILY_KINDS) from the executor's family event records alone
+    ([n, api.FAMILY_DESCRIPTORS[kind][0]] int64, numpy or torch), every table made ON THE DEVICE: (machine, chips, publics, global
+    events) in the shape of device_precompile_shard. The chip's table comes from api.tracegen_riscv_field_chip; an Fp or Fp2AddSub
+    shard mixes system calls, so its SyscallPrecompile rows take their ids from the events (the descriptor's syscall id is None)."""
+    from .. import api
+    if kind not in DEVICE_FAMILY_KINDS:
+        raise ValueError("no device builder for a %r shard: device_family_shard makes %s" % (kind, ", ".join(DEVICE_FAMILY_KINDS)))
+    words, syscall_id, arg2_word, segments = api.FAMILY_DESCRIPTORS[kind]
+    wide = lambda ev, n: {FAMILIES[kind][1]: api.tracegen_riscv_field_chip(kind, ev, RT.pad32(n), stream=stream)}
+    return _device_precompile_shard(events, words, wide, syscall_id, arg2_word, segments, prep, ctx, stream)
+
+
+def device_shard_of(executor, rec, prep, stream=None):
+    """device_shard for every kind with a device builder: DEVICE_SHARD_KINDS (device_shard) and DEVICE_FAMILY_KINDS
+    (device_family_shard). The three kinds that remain host-made (ed_add, ed_decompress, uint256_ops) raise ValueError."""
+    if rec.kind in DEVICE_FAMILY_KINDS:
+        return device_family_shard(rec.kind, rec.events, prep, rec.ctx, stream=stream)
+    if rec.kind in DEVICE_SHARD_KINDS:
+        return device_shard(executor, rec, prep, stream=stream)
+    raise ValueError("no device builder for a %r shard: device_shard_of makes %s" % (rec.kind, ", ".join(DEVICE_SHARD_KINDS + DEVICE_FAMILY_KINDS)))
 
 
 def execution_public_values(sh, prev=None):

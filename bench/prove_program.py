@@ -108,13 +108,12 @@ def main():
     ap.add_argument("--in-flight", type=int, default=0, help="after the shard-by-shard pass, prove ALL shards again through the library's "
                     "prover pool with this many proofs in flight (tables resident in HBM; proofs must equal the first pass's)")
     ap.add_argument("--only-kinds", default="", help="comma-separated shard kinds: build every shard, prove only these (a profile of one kind)")
-    ap.add_argument("--device-shard", action="store_true", help="core, memory and precompile shards (riscv_exec.DEVICE_SHARD_KINDS + DEVICE_FAMILY_KINDS): make the WHOLE shard on the device "
-                    "from the executor's records (riscv_exec.device_shard_of over run_records — device_core_shard: the event partition kernel, every chip's table, the public "
+    ap.add_argument("--device-shard", action="store_true", help="every shard of the run (riscv_exec.DEVICE_ANY_KINDS: core, memory and every precompile kind): make the WHOLE shard on the device "
+                    "from the executor's records (riscv_exec.device_shard_any over run_records — device_core_shard: the event partition kernel, every chip's table, the public "
                     "values' Global fields, the lookup counts; device_memory_shard: MemoryGlobalInit / Finalize from the run's address lists; "
-                    "device_precompile_shard / device_family_shard: the wide tables, SyscallPrecompile, MemoryLocal from the calls' event records) — no tracer and "
+                    "device_precompile_shard / device_family_shard / device_family_rest_shard: the wide tables, SyscallPrecompile, MemoryLocal from the calls' event records) — no tracer and "
                     "no host table is built for them; the public values are chained by the previous shard's, the Global events still join "
-                    "the run's balance check. ed_add, ed_decompress and uint256_ops keep the host "
-                    "path. MemoryBump's rows stand in another order than the host tracer's, so a core shard that crosses 2^24 cycles proves "
+                    "the run's balance check. MemoryBump's rows stand in another order than the host tracer's, so a core shard that crosses 2^24 cycles proves "
                     "to other bytes (the same statement)")
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--dry-run", action="store_true")
@@ -148,10 +147,10 @@ def main():
     t_prev = t_all
     for rec in X.run_records(ex, shard_cycles, core_limit=args.core_shards or None):
         kind, sh, tabs, device_chips = rec.kind, rec.executed, None, None
-        if args.device_shard and kind in X.DEVICE_SHARD_KINDS + X.DEVICE_FAMILY_KINDS:                # no tracer and no host table for these
+        if args.device_shard:                                           # every kind of shard: no tracer and no host table
             if pk_prep is None:
                 pk_prep = {n: to_col_major(t) for n, t in X.preprocessed_tables(ex, "cuda").items()}
-            machine, device_chips, publics, gev9 = X.device_shard_of(ex, rec, pk_prep)
+            machine, device_chips, publics, gev9 = X.device_shard_any(ex, rec, pk_prep)
             gev = X.global_events_11(gev9)
         else:
             machine, tabs, publics, gev = X.host_shard(ex, rec, device)

@@ -735,6 +735,41 @@ int sp1hip_tracegen_riscv_field_chip_width(uint32_t family);   /* -1: no device 
 int sp1hip_tracegen_riscv_field_chip(uint32_t family, uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events,
                                      sp1hip_stream_t stream);
 
+/* Device trace generation for the last three chips behind sp1hip_rv64_precompile_events, SP1HIP_RV64_FAMILY_* 12..14, from the
+ * executor's event records as they are (layouts below, at the family constants): EdAddAssign (ED_ADD, 44 u64 per event, width 1347),
+ * EdDecompress (ED_DECOMPRESS, 24 u64, width 1123) and Uint256Ops (UINT256_ADD_CARRY and UINT256_MUL_CARRY, which one call may mix: the
+ * row's operation is the low byte of word 3; 58 u64, width 477). The reference fills these tables on the host
+ * (crates/core/machine/src/syscall/precompiles/edwards, uint256_ops) and has no device filler for them. Output: column-major
+ * [width][height] Montgomery words, one row per event. A padding row is the reference's dummy row: EdAddAssign's field operations on
+ * four zero coordinates and EdDecompress' on y = 0, both with a zero head; Uint256Ops zero except the 63 witness columns, which hold
+ * the offset. The two Edwards tables are made in two launches through a work buffer of 8 x 40 (EdAddAssign) or 7 x 25 (EdDecompress)
+ * u32 per row, which the call allocates and releases itself in stream order (hipMallocAsync / hipFreeAsync on `stream`): the caller
+ * passes no scratch. Uint256Ops is one launch. Operands must be reduced, ED_ADD's denominators 1 +- d x1 x2 y1 y2 must not vanish and
+ * ED_DECOMPRESS' (y^2 - 1) / (d y^2 + 1) must be a square, which the executor guarantees; an event that breaks it neither faults nor
+ * takes longer, but its row satisfies no constraint system. All argument checks come before any launch: n_events <= height, a null
+ * pointer only with a zero count / height; height == 0 succeeds without a launch. The calls enqueue and return: they do not
+ * synchronise. */
+int sp1hip_tracegen_riscv_ed_add_width(void);          /* 1347 */
+int sp1hip_tracegen_riscv_ed_decompress_width(void);   /* 1123 */
+int sp1hip_tracegen_riscv_uint256_ops_width(void);     /* 477 */
+int sp1hip_tracegen_riscv_ed_add(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_ed_decompress(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream);
+int sp1hip_tracegen_riscv_uint256_ops(uint32_t* d_table, uint32_t height, const uint64_t* d_events, uint32_t n_events, sp1hip_stream_t stream);
+/* The MemoryLocal records { addr, initial clk, initial value, final clk, final value } of the words the calls of an ED_DECOMPRESS or
+ * a UINT256 carry shard touched, which the four segments of sp1hip_precompile_local_records cannot state (a pointer plus an offset;
+ * a register's constant address with its value and timestamp in separate words; six runs). family = SP1HIP_RV64_FAMILY_ED_DECOMPRESS
+ * or SP1HIP_RV64_FAMILY_UINT256_OPS, anything else is SP1HIP_ERROR_INVALID_ARGUMENT (ED_ADD is two plain segments). d_events:
+ * n_events x 24 / 58 u64. Records: n_events x 8 / 23, run after run, event by event inside each run —
+ *   ED_DECOMPRESS   the 4 x words at ptr + 8 i (pairs at event words 4 + 2 i, final clk + 1, final value word 20 + i), then the 4 y
+ *                   words at ptr + 32 + 8 i (pairs at 12 + 2 i, final clk, value unchanged);
+ *   UINT256 carry   registers 12, 13, 14 (addr = the register number, value word 4 + j, initial clk word 7 + j, final clk, value
+ *                   unchanged), then the blocks a, b, c, d, e of 4 words (pointers at event words 1, 2, 4, 5, 6; pairs at
+ *                   10 + 8 j + 2 i; final clk + j; a, b, c unchanged, d takes words 50..53, e words 54..57).
+ * records_capacity: the records d_records has room for; too few, more than 2^31 - 1 records, or a null pointer with records to write
+ * or events to read is SP1HIP_ERROR_INVALID_ARGUMENT before any launch. No events: success without a launch. */
+int sp1hip_precompile_touched_records(uint64_t* d_records, uint64_t records_capacity, const uint64_t* d_events, uint32_t n_events, uint32_t family,
+                                      sp1hip_stream_t stream);
+
 /* Device trace generation for the four chips of the SHA_EXTEND and SHA_COMPRESS precompile shards, from the executor's event records
  * as they are (sp1hip_rv64_sha_extend_events: n_events x 786 u64 on the device — [0] clk, [1] w_ptr, [2 + 11 r ..] step r < 48: four
  * (previous timestamp, word read) pairs for w[i-15], w[i-2], w[i-16], w[i-7], then w[i]'s previous timestamp, previous value and new

@@ -277,6 +277,13 @@ PROTOTYPES = [
     ("sp1hip_tracegen_riscv_field_chip_width", None, [C.c_uint32]),
     ("sp1hip_tracegen_riscv_field_chip", None, [C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_syscall_precompile_coded", None, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, _vp, _vp]),
+    ("sp1hip_tracegen_riscv_ed_add_width", None, []),
+    ("sp1hip_tracegen_riscv_ed_decompress_width", None, []),
+    ("sp1hip_tracegen_riscv_uint256_ops_width", None, []),
+    ("sp1hip_tracegen_riscv_ed_add", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_ed_decompress", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_tracegen_riscv_uint256_ops", None, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("sp1hip_precompile_touched_records", None, [_vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp]),
     ("sp1hip_tracegen_riscv_sha_extend_width", None, []),
     ("sp1hip_tracegen_riscv_sha_extend_control_width", None, []),
     ("sp1hip_tracegen_riscv_sha_compress_width", None, []),

@@ -908,6 +908,55 @@ def tracegen_riscv_syscall_precompile_coded(events, height, code_word=FAMILY_COD
     return ColMajor(out, int(height), SYSCALL_PRECOMPILE_WIDTH)
 
 
+ED_ADD_EVENT_WORDS, ED_DECOMPRESS_EVENT_WORDS, UINT256_OPS_EVENT_WORDS = 44, 24, 58     # FAMILY_WORDS of rv64_exec.cpp, families 12..14
+# the last three kinds of riscv_exec.FAMILIES, which tracegen_riscv_field_chip does not make, in the shape of PRECOMPILE_DESCRIPTORS
+# except for the last entry: the MemoryLocal segments of precompile_local_records (ed_add: _family_descriptor's), or the
+# SP1HIP_RV64_FAMILY_* that precompile_touched_records takes (ed_decompress: 8 records per call; uint256_ops: 23, and each row's
+# syscall id is its event's own: None). arg2 is word 2: ED_ADD's second pointer, ED_DECOMPRESS' sign bit, the carry calls' b pointer
+FAMILY_REST_DESCRIPTORS = {"ed_add": _family_descriptor(8, 2, 0x07), "ed_decompress": (ED_DECOMPRESS_EVENT_WORDS, 0x08, 2, 13),
+                           "uint256_ops": (UINT256_OPS_EVENT_WORDS, None, 2, 14)}
+TOUCHED_RECORDS_PER_CALL = {13: 8, 14: 23}
+
+
+def tracegen_riscv_ed_add(events, height, stream=None):
+    """`generate_trace_device` for the EdAddAssign chip (sp1hip_tracegen_riscv_ed_add): events = a device int64 tensor [n, 44] of the
+    executor's ED_ADD records (family "ed_add" of riscv_exec.ExecutedShard.precompile_events); one row per event, height >= n, padding
+    rows = the reference's dummy row. The call's work buffer is allocated and released inside it, on the stream. Returns the
+    column-major [1347][height] table as a ColMajor."""
+    return tracegen_riscv_records("EdAddAssign", events, height, stream)
+
+
+def tracegen_riscv_ed_decompress(events, height, stream=None):
+    """The same for the EdDecompress chip (sp1hip_tracegen_riscv_ed_decompress): events int64 [n, 24] (family "ed_decompress");
+    column-major [1123][height]."""
+    return tracegen_riscv_records("EdDecompress", events, height, stream)
+
+
+def tracegen_riscv_uint256_ops(events, height, stream=None):
+    """The same for the Uint256Ops chip (sp1hip_tracegen_riscv_uint256_ops): events int64 [n, 58] (family "uint256_ops": UINT256_ADD_CARRY
+    and UINT256_MUL_CARRY calls, told apart by the low byte of word 3); column-major [477][height]; a padding row is zero except for
+    the witness offset."""
+    return tracegen_riscv_records("Uint256Ops", events, height, stream)
+
+
+def precompile_touched_records(events, family, stream=None):
+    """The MemoryLocal records of the words the calls of an ed_decompress (family 13) or a uint256_ops (14) shard touched
+    (sp1hip_precompile_touched_records): events = a device int64 tensor [n, 24 / 58]. Returns a device int64 tensor [n * 8 / 23, 5]
+    { addr, initial clk, initial value, final clk, final value }, run after run, event by event inside each: what
+    riscv_more_trace.family_shard_from hands _close_precompile_shard, and what tracegen_riscv_memory_local reads."""
+    if family not in TOUCHED_RECORDS_PER_CALL:
+        raise ValueError("precompile_touched_records makes the records of family 13 (ed_decompress) and 14 (uint256_ops), not of %r" % (family,))
+    n = int(events.shape[0])
+    words = FAMILY_REST_DESCRIPTORS["ed_decompress" if family == 13 else "uint256_ops"][0]
+    assert events.dtype == torch.int64 and events.dim() == 2 and events.shape[1] == words and (n == 0 or (events.is_cuda and events.is_contiguous()))
+    total = n * TOUCHED_RECORDS_PER_CALL[family]
+    device = events.device if events.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.stream(stream or torch.cuda.current_stream()):
+        out = torch.empty((total, MEMORY_LOCAL_RECORD_WORDS), dtype=torch.int64, device=device)
+    check(_L().sp1hip_precompile_touched_records(_dptr(out) if total else None, total, _dptr(events) if n else None, n, int(family), _stream_ptr(stream)))
+    return out
+
+
 # chip: (entry point, u64 words of a record, leading chip argument or None) — every chip whose table is made from its record stream
 # alone, the wrappers above by chip name (MemoryLocal, MemoryGlobal*, SyscallCore and SyscallPrecompile also write Global events)
 RISCV_TRACEGEN = {**{c: ("sp1hip_tracegen_riscv_alu", ALU_EVENT_WORDS, k) for c, k in RISCV_ALU_CHIPS.items()},
@@ -925,7 +974,10 @@ RISCV_TRACEGEN = {**{c: ("sp1hip_tracegen_riscv_alu", ALU_EVENT_WORDS, k) for c,
                   "ShaCompress": ("sp1hip_tracegen_riscv_sha_compress", SHA_COMPRESS_EVENT_WORDS, None),
                   "ShaCompressControl": ("sp1hip_tracegen_riscv_sha_compress_control", SHA_COMPRESS_EVENT_WORDS, None),
                   "Poseidon2": ("sp1hip_tracegen_riscv_poseidon2", POSEIDON2_EVENT_WORDS, None),
-                  "Uint256MulMod": ("sp1hip_tracegen_riscv_uint256_mul", UINT256_EVENT_WORDS, None)}
+                  "Uint256MulMod": ("sp1hip_tracegen_riscv_uint256_mul", UINT256_EVENT_WORDS, None),
+                  "EdAddAssign": ("sp1hip_tracegen_riscv_ed_add", ED_ADD_EVENT_WORDS, None),
+                  "EdDecompress": ("sp1hip_tracegen_riscv_ed_decompress", ED_DECOMPRESS_EVENT_WORDS, None),
+                  "Uint256Ops": ("sp1hip_tracegen_riscv_uint256_ops", UINT256_OPS_EVENT_WORDS, None)}
 
 
 def tracegen_riscv_records(chip, records, height, stream=None):

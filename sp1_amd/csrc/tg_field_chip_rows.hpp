@@ -38,8 +38,8 @@ using tgf::U;
 enum : uint32_t { KIND_ADD = 0, KIND_SUB = 1, KIND_MUL = 2, KIND_DIV = 3 };     // a record's last word; the low three are an Fp call's code - base
 
 // ------------------------------------------------------------------------------------------------------------ the work buffer
-template <int N> struct Work {
-    static constexpr int REC = 3 * N + 1;                          // a[N], b[N], r[N], kind
+template <int N, int WORDS = 3 * N + 1> struct Work {
+    static constexpr int REC = WORDS;                              // a[N], b[N], r[N], kind; EdAddAssign's (tg_ed_uint256_rows.hpp) has five operands
     static size_t words(uint32_t height, uint32_t ops) { return (size_t)ops * REC * height; }
 };
 TG_HD uint32_t work_word(const uint32_t* work, size_t i) {

@@ -694,10 +694,11 @@ def device_precompile_shard(kind, events, prep, ctx, stream=None):
 
 
 def _device_precompile_shard(events, words, wide, syscall_id, arg2_word, segments, prep, ctx, stream):
-    """The body device_precompile_shard and device_family_shard share: the events uploaded as they are, the kind's wide tables
-    (wide(events, n) -> {chip: ColMajor}), SyscallPrecompile into the tail of MemoryLocal's Global events — one `syscall_id` for all
-    rows, or None for each event's own code (api.tracegen_riscv_syscall_precompile_coded) —, MemoryLocal from the touched words'
-    records, Global, the public values, the counted tables."""
+    """The body device_precompile_shard, device_family_shard and device_family_rest_shard share: the events uploaded as they are, the
+    kind's wide tables (wide(events, n) -> {chip: ColMajor}), SyscallPrecompile into the tail of MemoryLocal's Global events — one
+    `syscall_id` for all rows, or None for each event's own code (api.tracegen_riscv_syscall_precompile_coded) —, MemoryLocal from the
+    touched words' records — `segments`: those of api.precompile_local_records, or a callback events -> records —, Global, the public
+    values, the counted tables."""
     from .. import api
     with torch.cuda.stream(stream or torch.cuda.current_stream()):
         ev = _on_device(events, words)
@@ -709,7 +710,8 @@ def _device_precompile_shard(events, words, wide, syscall_id, arg2_word, segment
         else:
             syscalls = lambda tail: api.tracegen_riscv_syscall_precompile(ev, RT.pad32(n), syscall_id, arg2_word, global_events=tail, stream=stream)
         pv = PVM.no_memory_events(PVM.initialized_state(ctx.pc_start))
-        gev, _, _ = _local_and_global_tables(made, api.precompile_local_records(ev, segments, stream=stream), n, stream, pv=pv,
+        records = segments(ev) if callable(segments) else api.precompile_local_records(ev, segments, stream=stream)
+        gev, _, _ = _local_and_global_tables(made, records, n, stream, pv=pv,
                                              fill=lambda tail: made.update(SyscallPrecompile=syscalls(tail)))
         publics = PVM.to_tensor(pv)
         machine, chips = _close_device_shard(made, prep, RT.smallest_cluster(set(made) | set(prep)), publics, ctx, stream)
@@ -751,12 +753,45 @@ def device_family_shard(kind, events, prep, ctx, stream=None):
 
 def device_shard_of(executor, rec, prep, stream=None):
     """device_shard for every kind with a device builder: DEVICE_SHARD_KINDS (device_shard) and DEVICE_FAMILY_KINDS
-    (device_family_shard). The three kinds that remain host-made (ed_add, ed_decompress, uint256_ops) raise ValueError."""
+    (device_family_shard). The last three kinds (ed_add, ed_decompress, uint256_ops) raise ValueError here: device_shard_any, below,
+    covers them too."""
     if rec.kind in DEVICE_FAMILY_KINDS:
         return device_family_shard(rec.kind, rec.events, prep, rec.ctx, stream=stream)
     if rec.kind in DEVICE_SHARD_KINDS:
         return device_shard(executor, rec, prep, stream=stream)
     raise ValueError("no device builder for a %r shard: device_shard_of makes %s" % (rec.kind, ", ".join(DEVICE_SHARD_KINDS + DEVICE_FAMILY_KINDS)))
+
+
+DEVICE_FAMILY_REST_KINDS = ("ed_add", "ed_decompress", "uint256_ops")     # the last three FAMILIES; their descriptors are api.FAMILY_REST_DESCRIPTORS
+
+
+def device_family_rest_shard(kind, events, prep, ctx, stream=None):
+    """A provable precompile shard of `kind` (DEVICE_FAMILY_REST_KINDS) from the executor's family event records alone ([n, 44 / 24 /
+    58] int64, numpy or torch), every table made ON THE DEVICE: (machine, chips, publics, global events) in the shape of
+    device_precompile_shard. The chip's table comes from api.tracegen_riscv_ed_add / _ed_decompress / _uint256_ops; the touched words'
+    records of ed_decompress and uint256_ops from api.precompile_touched_records (ed_add's are two plain segments); a uint256_ops shard
+    mixes two system calls, so its SyscallPrecompile rows take their ids from the events."""
+    from .. import api
+    if kind not in DEVICE_FAMILY_REST_KINDS:
+        raise ValueError("no device builder for a %r shard: device_family_rest_shard makes %s" % (kind, ", ".join(DEVICE_FAMILY_REST_KINDS)))
+    words, syscall_id, arg2_word, local = api.FAMILY_REST_DESCRIPTORS[kind]
+    chip = FAMILIES[kind][1]
+    wide = lambda ev, n: {chip: api.tracegen_riscv_records(chip, ev, RT.pad32(n), stream=stream)}
+    segments = local if isinstance(local, tuple) else (lambda ev: api.precompile_touched_records(ev, local, stream=stream))
+    return _device_precompile_shard(events, words, wide, syscall_id, arg2_word, segments, prep, ctx, stream)
+
+
+DEVICE_ANY_KINDS = DEVICE_SHARD_KINDS + DEVICE_FAMILY_KINDS + DEVICE_FAMILY_REST_KINDS       # every kind run_records yields
+
+
+def device_shard_any(executor, rec, prep, stream=None):
+    """device_shard for every kind of shard a run can have: DEVICE_SHARD_KINDS (device_shard), DEVICE_FAMILY_KINDS (device_family_shard)
+    and DEVICE_FAMILY_REST_KINDS (device_family_rest_shard). Only an unknown kind raises ValueError."""
+    if rec.kind in DEVICE_FAMILY_REST_KINDS:
+        return device_family_rest_shard(rec.kind, rec.events, prep, rec.ctx, stream=stream)
+    if rec.kind in DEVICE_FAMILY_KINDS + DEVICE_SHARD_KINDS:
+        return device_shard_of(executor, rec, prep, stream=stream)
+    raise ValueError("no device builder for a %r shard: device_shard_any makes %s" % (rec.kind, ", ".join(DEVICE_ANY_KINDS)))
 
 
 def execution_public_values(sh, prev=None):

@@ -115,6 +115,9 @@ def main():
                     "no host table is built for them; the public values are chained by the previous shard's, the Global events still join "
                     "the run's balance check. MemoryBump's rows stand in another order than the host tracer's, so a core shard that crosses 2^24 cycles proves "
                     "to other bytes (the same statement)")
+    ap.add_argument("--check", action="store_true", help="before each proof, check the shard's device tables where they are: every constraint on every row and every "
+                    "bus (riscv_exec.check_device_shard: sp1hip_check_constraints / sp1hip_check_interactions). Outside every timed region; each "
+                    "row gains check_ms and check: \"ok\" or the findings")
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--out", default="")
@@ -126,6 +129,7 @@ def main():
     from sp1_amd.machines import public_values as PVM, riscv_exec as X, riscv_trace as RT
     device = "cpu" if args.dry_run else "cuda"
     assert not (args.dry_run and args.device_shard), "--device-shard makes the tables on the GPU: there is nothing to dry-run"
+    assert not (args.dry_run and args.check), "--check checks the device tables: there are none in a dry run"
     if not args.dry_run:
         from core_real import to_col_major
         import ctypes as C
@@ -194,6 +198,13 @@ def main():
                 chips = [(a, i, to_col_major(tabs[a.name][1]), pk_prep.get(a.name)) for a, i in machine]
             if tabs is not None:
                 tabs.clear()
+            if args.check:                                                                # untimed: before the proof, after build_s and setup_ms
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                failing, imbalance = X.check_device_shard(machine, chips, publics)
+                row["check_ms"] = round(1e3 * (time.perf_counter() - t0), 2)
+                row["check"] = "ok" if not failing and not imbalance else {"failing": failing, "imbalance": [[list(map(str, k)) if isinstance(k, tuple) else k, v]
+                                                                                                             for k, v in list(imbalance.items())[:32]]}
             pv = RT.to_monty_np(publics)
             commit = pk.preprocessed_commit
             if kind not in warmed:
@@ -231,7 +242,7 @@ def main():
         if args.max_shards and len(shards) >= args.max_shards:
             break
         t_prev = time.perf_counter()
-    wall = time.perf_counter() - t_all
+    wall = time.perf_counter() - t_all - sum(s.get("check_ms", 0.0) for s in shards) / 1e3     # --check is outside every timed region
     whole = (not args.max_shards or len(shards) < args.max_shards) and not args.core_shards and not args.only_kinds
     if args.core_shards:                                     # the cycles of the core shards that were executed but not proved
         out_note = "core shards beyond the first %d executed, not proved" % args.core_shards

@@ -869,6 +869,66 @@ int sp1hip_lookup_count_program(const uint64_t* d_pcs, uint64_t stride_words, ui
                                 uint32_t* d_program_counts, uint32_t* d_status, uint32_t tag, sp1hip_stream_t stream);
 int sp1hip_lookup_counts_finish(uint32_t* d_counts, uint64_t n_cells, uint32_t* d_table_or_null, uint32_t* d_status, sp1hip_stream_t stream);
 
+/* ---------------------------------------------------------------- device trace checker (sp1_amd/csrc/trace_check.hip)
+ * Every constraint of every chip on every real row of the device tables a shard proof is about to be made from: what the reference
+ * does under cfg(sp1_debug_constraints) in `prove_shard_with_data` (`debug_constraints_all_chips`,
+ * /root/reference/crates/hypercube/src/prover/shard.rs:L711-L720, crates/hypercube/src/debug.rs:L27-L125). A call of its own: no
+ * prover path reads it and nothing switches it on inside one.
+ *
+ * sp1hip_check_constraints takes the chip array of sp1hip_prove_shard (program, widths, d_main, d_prep, real_rows of each chip;
+ * names and interaction words are not read) and the public values as Montgomery words, evaluates the caller's plain SSA — HINT
+ * pseudo-instructions dropped, none of the zerocheck's fused pieces — one row per lane, and fills one report per chip,
+ * SP1HIP_CHECK_REPORT_WORDS u64 words each in `reports`, in this order: failing_rows, first_row, noncanonical, fail_count_offset,
+ * row_offset, pieces, registers, lanes, n_first, first_constraints[64]. What they hold:
+ *   failing_rows        rows on which at least one constraint is non-zero
+ *   first_row           the smallest of them; UINT64_MAX when there is none
+ *   noncanonical        main and preprocessed words that are >= p (no field element's stored form; constraint values of a table
+ *                       that holds one mean nothing)
+ *   n_first, first_constraints   the constraints that are non-zero on first_row, ascending, at most 64 of them
+ *   pieces, registers, lanes     how the program ran: the pieces it was cut into (1 unless it needs more than 512 registers), the
+ *                       largest piece's register count, rows per workgroup
+ *   fail_count_offset   where in h_words the chip's num_constraints words start: fail_count[k] = rows on which constraint k is non-zero
+ *   row_offset          where in h_words the main_width + prep_width Montgomery words of first_row start (main, then
+ *                       preprocessed; zeros when no row fails)
+ * A chip with no rows or no constraints reports zeros. h_words / *n_words: the size protocol of the other entry points (too small,
+ * or NULL: SP1HIP_ERROR_BUFFER_TOO_SMALL and *n_words = the sum over the chips of num_constraints + main_width + prep_width, before
+ * any device work). A malformed program (an opcode, an operand that is not an earlier value, a column outside its table, a public
+ * value index at or above n_publics, num_constraints other than the number of asserts) is SP1HIP_ERROR_INVALID_ARGUMENT before any
+ * launch. The call synchronises the stream.
+ *
+ * sp1hip_trace_check_compile (host only): the compiled form the kernel and the host loop of tests/native/trace_check.hip run
+ * (layout: sp1_amd/csrc/tc_rows.hpp), cut for a budget of max_regs registers (0: the default, 512). Size protocol on
+ * out_words / *n_words. */
+#define SP1HIP_CHECK_REPORT_WORDS 73   /* u64 words per chip: nine fields, then first_constraints[64] (the order is given above) */
+int sp1hip_check_constraints(const sp1hip_shard_chip_t* chips, int n_chips, const uint32_t* h_publics, int n_publics,
+                             uint64_t* reports, uint32_t* h_words, size_t* n_words, sp1hip_stream_t stream);
+int sp1hip_trace_check_compile(const uint32_t* program, uint32_t n_instr, uint32_t main_width, uint32_t prep_width, uint32_t num_constraints,
+                               uint32_t max_regs, uint32_t* out_words, size_t* n_words);
+
+/* Every bus of the shard: do the sends and receives of all chips cancel as a multiset of (kind, values)? The reference's
+ * `debug_interactions_with_all_chips` (/root/reference/crates/hypercube/src/logup_gkr/prover.rs:L99-L135,
+ * crates/hypercube/src/lookup/debug.rs:L48-L200) without a host copy of any table. chips: the same array (interaction words, widths,
+ * d_main, d_prep, real_rows are read); the caller appends the machine's eval_public_values as one more chip with a one-row table
+ * that holds the public values.
+ *   Pass 1 evaluates every interaction on every row, one row per lane. A message with a non-zero multiplicity m is folded into two
+ *   independent 64-bit hashes of (kind, number of values, canonical values), and m — or m - p when m > p / 2 —, negated for a
+ *   receive, is added (device-scope 64-bit atomic adds, lanes of a wave that hold one bucket combined into one add first) to one
+ *   bucket in each of two tables of 2^log_buckets signed sums (log_buckets 1..26; 22 is the library's usual value: 64 MB).
+ *   Verdict: balanced = every bucket of both tables is 0 mod p. A balanced shard is never called unbalanced. A wrong "balanced" needs
+ *   the discrepancies of the unbalanced keys to cancel bucket by bucket in BOTH tables: with k unbalanced keys, some pair must share
+ *   a bucket in each (two independent hashes: of order k^2 / 2^(2 log_buckets)) and their discrepancies must then sum to 0 mod p.
+ *   Pass 2 (only when the first table has a non-zero bucket) evaluates the messages again and writes a 4-word record — chip index,
+ *   interaction index, row, canonical multiplicity — for every message whose bucket of the first table is non-zero: every message
+ *   of an unbalanced key, and whatever balanced messages share such a bucket (the caller's exact tally cancels those). `cap`
+ *   records fit h_records; records_wanted counts them all, records = min(records_wanted, cap) were written, truncated says that
+ *   some were left out (an arbitrary subset is kept; the verdict stands).
+ * A malformed description is SP1HIP_ERROR_INVALID_ARGUMENT before any launch, by the parser sp1hip_lookup_count_sends uses. The call
+ * synchronises the stream. */
+#define SP1HIP_CHECK_BUSES_WORDS 8      /* u64 words of `report`: messages, nonzero buckets of the first and of the second table,
+                                         * records_wanted, records, balanced (0 / 1), truncated (0 / 1), one spare */
+int sp1hip_check_interactions(const sp1hip_shard_chip_t* chips, int n_chips, uint32_t log_buckets, uint64_t* report,
+                              uint32_t* h_records, uint64_t cap, sp1hip_stream_t stream);
+
 /* ---------------------------------------------------------------- guest execution (host code, no device work)
  * An rv64im executor for SP1 guest ELFs: what `MinimalExecutor` + `TracingVM` do for the core prover
  * (/root/reference/crates/core/executor/src/minimal.rs, tracing.rs:L57-L147, vm.rs:L139-L431; the controller's shard loop is

@@ -53,6 +53,9 @@ class ShardChip(C.Structure):
                 ("real_rows", C.c_uint64)]
 
 
+CHECK_REPORT_WORDS, CHECK_BUSES_WORDS = 73, 8          # u64 words of a chip's constraint report / of the bus report (include/sp1hip.h)
+
+
 class PoolChip(C.Structure):
     _fields_ = [("name", C.c_char_p), ("program", C.POINTER(C.c_uint32)), ("n_instr", C.c_uint32),
                 ("num_constraints", C.c_uint32), ("interactions", C.POINTER(C.c_uint32)), ("n_words", C.c_uint32),
@@ -299,6 +302,9 @@ PROTOTYPES = [
     ("sp1hip_lookup_count_sends", None, [u32p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, _vp]),
     ("sp1hip_lookup_count_program", None, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, _vp, _vp, C.c_uint32, _vp]),
     ("sp1hip_lookup_counts_finish", None, [_vp, C.c_uint64, _vp, _vp, _vp]),
+    ("sp1hip_check_constraints", None, [C.POINTER(ShardChip), _int, u32p, _int, C.POINTER(C.c_uint64), u32p, C.POINTER(_sz), _vp]),
+    ("sp1hip_trace_check_compile", None, [u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.POINTER(_sz)]),
+    ("sp1hip_check_interactions", None, [C.POINTER(ShardChip), _int, C.c_uint32, C.POINTER(C.c_uint64), u32p, C.c_uint64, _vp]),
     ("sp1hip_rv64_create", None, [u8p, C.c_uint64, C.POINTER(_vp)]),
     ("sp1hip_rv64_destroy", "void", [_vp]),
     ("sp1hip_rv64_write_stdin", None, [_vp, u8p, C.c_uint64]),

@@ -1068,6 +1068,85 @@ class LookupCounter:
         return {"Byte": ColMajor(byte, 1 << 16, 6), "Range": ColMajor(rng, 1 << 17, 1), "Program": ColMajor(prog, self.program_height, 1)}
 
 
+def check_constraints(chips, public_values, stream=None):
+    """Every constraint of every chip on every row, on the device (sp1hip_check_constraints: the reference's
+    `debug_constraints_all_chips`, hypercube/src/debug.rs:L27-L125). chips: the [(AirProgram, InteractionProgram, main ColMajor or
+    None, prep ColMajor or None)] of prove_shard; public_values: Montgomery words. No table is copied to the host: per chip one dict
+    comes back — name, failing_rows, first_row (None when no row fails), fail_count (uint32 per constraint: the rows on which it is
+    non-zero), noncanonical (stored words >= p), first_constraints (the indices non-zero on first_row, at most 64), first_row_main /
+    first_row_prep (that row's Montgomery words), pieces / registers / lanes (how the program ran). Synchronises the stream."""
+    arr, keep = _shard_chip_array(chips)
+    pv = np.ascontiguousarray(np.asarray(public_values, dtype=np.uint32).reshape(-1))
+    reports = np.zeros((max(len(chips), 1), _lib.CHECK_REPORT_WORDS), dtype=np.uint64)
+    n = C.c_size_t(sum(a.num_constraints + a.main_width + a.prep_width for a, _, _, _ in chips))
+    words = np.zeros(max(n.value, 1), dtype=np.uint32)
+    check(_L().sp1hip_check_constraints(arr, len(chips), pv.ctypes.data_as(_lib.u32p) if pv.size else None, int(pv.size),
+                                        reports.ctypes.data_as(C.POINTER(C.c_uint64)), words.ctypes.data_as(_lib.u32p), C.byref(n), _stream_ptr(stream)))
+    out = []
+    for (air, _, _, _), r in zip(chips, reports.tolist()):
+        failing_rows, first_row, noncanonical, fc, row, pieces, registers, lanes, n_first = r[:9]
+        failed = failing_rows != 0
+        out.append({"name": air.name, "failing_rows": failing_rows, "first_row": first_row if failed else None,
+                    "fail_count": words[fc:fc + air.num_constraints].copy(), "noncanonical": noncanonical,
+                    "first_constraints": r[9:9 + n_first],
+                    "first_row_main": words[row:row + air.main_width].copy() if failed else None,
+                    "first_row_prep": words[row + air.main_width:row + air.main_width + air.prep_width].copy() if failed and air.prep_width else None,
+                    "pieces": pieces, "registers": registers, "lanes": lanes})
+    return out
+
+
+def check_interactions(chips, cap=1 << 16, log_buckets=22, stream=None):
+    """Do the sends and receives of the chips cancel, bus by bus (sp1hip_check_interactions: the reference's
+    `debug_interactions_with_all_chips`, hypercube/src/lookup/debug.rs:L48-L200)? chips: the tuples of check_constraints, with the
+    machine's eval_public_values appended by the caller as one more chip over a one-row table (riscv_exec.check_device_shard does).
+    The device tallies signed multiplicities in two tables of 2^log_buckets buckets under two independent hashes and names, in at
+    most `cap` records, the messages whose bucket of the first table does not cancel; this function fetches the rows those records
+    name (and no other cell of any table), evaluates their messages with VCol.apply and sums them exactly. Returns {"balanced",
+    "truncated", "messages", "nonzero_buckets", "records_wanted", "records" (uint32 [n, 4]: chip, interaction, row, canonical
+    multiplicity), "imbalance": {(kind, values...): discrepancy mod p} over the keys that do not cancel}. When nothing was truncated
+    the imbalance is the whole truth: balanced keys that merely share a bucket cancel in the exact tally and drop out."""
+    arr = (ShardChip * max(len(chips), 1))()
+    keep = []
+    for i, (_, inter, main, prep) in enumerate(chips):         # the widths are the InteractionProgram's (eval_public_values' AirProgram has no columns)
+        words = np.ascontiguousarray(inter.to_array(), dtype=np.uint32)
+        keep.append(words)
+        rows = main.height if main is not None else 0
+        assert rows == 0 or (main.width == inter.main_width and (prep.width if prep is not None else 0) == inter.prep_width), inter.name
+        arr[i] = ShardChip(inter.name.encode(), None, 0, 0, words.ctypes.data_as(_lib.u32p), words.size, inter.main_width, inter.prep_width,
+                           C.c_void_p(main.words.data_ptr()) if rows and inter.main_width else None,
+                           C.c_void_p(prep.words.data_ptr()) if prep is not None and rows and inter.prep_width else None, rows)
+    report = np.zeros(_lib.CHECK_BUSES_WORDS, dtype=np.uint64)
+    records = np.zeros((max(int(cap), 1), 4), dtype=np.uint32)
+    check(_L().sp1hip_check_interactions(arr, len(chips), int(log_buckets), report.ctypes.data_as(C.POINTER(C.c_uint64)), records.ctypes.data_as(_lib.u32p), int(cap),
+                                        _stream_ptr(stream)))
+    messages, nonzero_a, nonzero_b, records_wanted, n_records, balanced, truncated = report.tolist()[:7]
+    records = records[:n_records]
+    tally = {}
+    r_inv = pow(1 << 32, -1, P)
+    for ci in np.unique(records[:, 0]):
+        _, it, main, prep = chips[int(ci)]
+        mine = records[records[:, 0] == ci]
+        rows, where = np.unique(mine[:, 2], return_inverse=True)
+        index = torch.as_tensor(rows.astype(np.int64), device=main.words.device)
+
+        def fetch(t):                                          # the named rows of a column-major table, canonical, [n][width]
+            if t is None or t.width == 0:
+                return np.zeros((len(rows), 0), dtype=np.uint64)
+            got = t.words.view(t.width, t.height).index_select(1, index).cpu().numpy().view(np.uint32).astype(np.uint64)
+            return (got * np.uint64(r_inv) % np.uint64(P)).T
+
+        main_rows, prep_rows = fetch(main), fetch(prep)
+        both = [(1, x) for x in it.sends] + [(-1, x) for x in it.receives]
+        for (_, k, _, m), w in zip(mine.tolist(), where.tolist()):
+            sign, (kind, values, mult) = both[k]
+            assert mult.apply(prep_rows[w], main_rows[w]) == m, "a record's multiplicity is not its row's"
+            key = (kind,) + tuple(v.apply(prep_rows[w], main_rows[w]) for v in values)
+            tally[key] = (tally.get(key, 0) + sign * m) % P
+    return {"balanced": bool(balanced), "truncated": bool(truncated), "messages": messages, "nonzero_buckets": (nonzero_a, nonzero_b),
+            "records_wanted": records_wanted,
+            "records": records, "imbalance": {k: v for k, v in tally.items() if v}}
+
+
 class ProvingKey:
     """`ProvingKey` of the AirProver slot: the preprocessed commitment round + the verifying key (sp1hip_setup).
     Keeps the preprocessed device tables alive."""

@@ -97,8 +97,13 @@ TG_HD bool lc_program_cell(uint64_t pc, uint64_t pc_base, uint32_t n_instruction
 }
 
 // Host: interaction words -> compiled form. Returns nullptr, or what is wrong with the description (nothing is appended to a
-// meaningful `out` then). Sends of kind BYTE are kept; receives and other kinds are parsed, checked and skipped.
-inline const char* lc_compile(const uint32_t* words, size_t n_words, uint32_t main_width, uint32_t prep_width, std::vector<uint32_t>& out) {
+// meaningful `out` then). every == false (lc_compile): sends of kind BYTE are kept; receives and other kinds are parsed, checked and
+// skipped. every == true (the trace checker's bus tally, tc_rows.hpp): EVERY interaction is kept, with three more words in front of
+// its forms — [interaction index, words in this record, is_send, kind, n_values, form(m), form(value 0), ...] — and any number of
+// values up to LC_MAX_VALUES. One parser, so both refuse the same descriptions.
+constexpr uint32_t LC_MAX_VALUES = 4096;
+inline const char* lc_compile_interactions(const uint32_t* words, size_t n_words, uint32_t main_width, uint32_t prep_width, bool every,
+                                           std::vector<uint32_t>& out) {
     out.assign(1, 0u);
     if (!words || n_words < 1) return "the description has no interaction count";
     size_t at = 1;
@@ -109,10 +114,12 @@ inline const char* lc_compile(const uint32_t* words, size_t n_words, uint32_t ma
         const uint32_t is_send = words[at], kind = words[at + 1], n_values = words[at + 2];
         at += 3;
         if (is_send > 1) return "an interaction is neither a send nor a receive";
-        const bool keep = is_send == 1 && kind == LC_KIND_BYTE;
-        if (keep && n_values != 4) return "a byte message with other than 4 values";
+        const bool keep = every || (is_send == 1 && kind == LC_KIND_BYTE);
+        if (keep && !every && n_values != 4) return "a byte message with other than 4 values";
+        if (every && n_values > LC_MAX_VALUES) return "a message with more than 4096 values";
         const size_t head = out.size();
         if (keep) { out.push_back(k); out.push_back(0u); }
+        if (every) { out.push_back(is_send); out.push_back(kind); out.push_back(n_values); }
         for (uint64_t f = 0; f < (uint64_t)n_values + 1; f++) {
             if (n_words - at < 2) return "the word list ends inside an affine form";
             const uint32_t n_terms = words[at], constant = words[at + 1];
@@ -132,6 +139,10 @@ inline const char* lc_compile(const uint32_t* words, size_t n_words, uint32_t ma
     }
     if (at != n_words) return "words after the last interaction";
     return nullptr;
+}
+
+inline const char* lc_compile(const uint32_t* words, size_t n_words, uint32_t main_width, uint32_t prep_width, std::vector<uint32_t>& out) {
+    return lc_compile_interactions(words, n_words, main_width, prep_width, false, out);
 }
 
 }  // namespace tg

@@ -770,6 +770,32 @@ int zc_get_plan(const uint32_t* program, uint32_t n_instr, uint32_t main_width, 
     return SP1HIP_SUCCESS;
 }
 
+int zc_plain_pieces(const uint32_t* program, uint32_t n_instr, uint32_t main_width, uint32_t prep_width, uint32_t max_regs,
+                    std::vector<Chunk>* pieces) {
+    pieces->clear();
+    std::vector<uint32_t> clean(program, program + (size_t)n_instr * 3), folded, tagged;
+    for (uint32_t k = 0; k < n_instr; k++)                       // a HINT defines no value: a constant nobody reads, as in zc_get_plan
+        if (clean[3 * k] == ZC_HINT) { clean[3 * k] = ZC_CONST; clean[3 * k + 1] = 0; clean[3 * k + 2] = 0; }
+    fold_immediates(clean.data(), n_instr, &folded);
+    schedule_program(folded.data(), n_instr, main_width, 0, &tagged);      // mode 0: the caller's order, asserts tagged with their index
+    // the cut: halve the instruction target until every piece's file fits (build_chunks closes a piece at an assert boundary and
+    // re-emits the cone of the next one's asserts)
+    for (uint32_t limit = 0xffffffffu;;) {
+        std::vector<Chunk> cut;
+        SP1HIP_TRY(build_chunks(tagged.data(), n_instr, main_width, prep_width, limit, &cut, limit));
+        // the GKR bookkeeping of the zerocheck (TOUCH pseudo-chunks for columns no constraint reads) is not the checker's business
+        cut.erase(std::remove_if(cut.begin(), cut.end(), [](const Chunk& c) { return c.prog.empty() || (c.prog[0] & 0xffu) == ZC_TOUCH; }), cut.end());
+        uint32_t regs = 0;
+        for (const Chunk& c : cut) regs = std::max(regs, c.n_regs);
+        if (regs <= max_regs) { pieces->swap(cut); return SP1HIP_SUCCESS; }
+        limit = (limit == 0xffffffffu ? n_instr : limit) / 2;
+        if (limit < 8) {
+            set_error("zc_plain_pieces: one constraint alone needs %u registers, more than the budget of %u", regs, max_regs);
+            return SP1HIP_ERROR_INVALID_ARGUMENT;
+        }
+    }
+}
+
 Ext zc_eval_zero_row(const ZcPlan& plan, const Ext* alpha_pows, const uint32_t* publics) {
     Ext acc = kb::ext_zero();
     eval_words_row(plan.prog.data(), plan.prog.size() / 4, plan.n_regs, nullptr, nullptr, publics,

@@ -66,6 +66,14 @@ constexpr uint32_t ZC_FINE_LIMIT = 32, ZC_FINE_MAX_TERMS = 64;
 int zc_get_plan(const uint32_t* program, uint32_t n_instr, uint32_t main_width, uint32_t prep_width, int chip_index,
                 std::shared_ptr<const ZcPlan>* out, uint64_t rows = ~0ull);
 
+// The plain SSA of `program` for the trace checker (trace_check.hip): HINT pseudo-instructions dropped, the caller's instruction
+// order, immediates folded, registers allocated — and cut at assert boundaries into self-contained pieces of at most `max_regs`
+// registers each (one piece when the whole program fits; a value two pieces need is recomputed in both). Every ASSERT_ZERO
+// carries its index in the WHOLE program in operand b. No macro, no fused piece, no reordering: nothing of what a ZcPlan proves
+// with. The program must already be known to be in SSA order with valid opcodes (validate_program of trace_check.hip does that for the checker).
+int zc_plain_pieces(const uint32_t* program, uint32_t n_instr, uint32_t main_width, uint32_t prep_width, uint32_t max_regs,
+                    std::vector<Chunk>* pieces);
+
 // host evaluation of the whole program on an all-zero row (padded_row_adjustment, shard.rs:L524-L536): sum_k alpha_pows[k] * (the
 // value of constraint k)
 Ext zc_eval_zero_row(const ZcPlan& plan, const Ext* alpha_pows, const uint32_t* publics);
